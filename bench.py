@@ -18,7 +18,12 @@ is BASELINE config C4) plus the de-dup all_to_all, the tail all_gather and
 the RCCL all_reduce of the count vector.  value = reads processed by all
 ranks / max-over-ranks wall time of the K timed steps.
 
-Also reported: `roofline` of the dominant kernel (k_mam_sm: algorithmic bytes
+A plain run does only that: set-up (the genome from tools/genome_cache.py's
+cache where build() left one), warm-up, the K timed steps, the result line.
+--dump-outputs DIR also writes what the last timed step computed (the bin
+counts and the run's counters; float64 .npy), the same from run to run.
+
+With --full, also reported: `roofline` of the dominant kernel (k_mam_sm: algorithmic bytes
 = 64 B x the line transitions of the kernel's own probe sequence, counted by
 running the kernel source on the host (tools/sm_emu) over the downloaded index
 for a sample of the same reads, over the HIP-event-timed kernel duration),
@@ -94,6 +99,36 @@ def host_cores():
 
 def log(*a):
     print("[bench %s]" % time.strftime("%H:%M:%S"), *a, file=sys.stderr, flush=True)
+
+
+def genome_start(kind):
+    """The genome and its doubled text, begun on a thread of their own (a
+    cached genome is file reads, which run beside the imports and the
+    device's start-up): a future of (contigs, (T, sp, sz, names))."""
+    from concurrent.futures import ThreadPoolExecutor
+    import genome_cache
+    ex = ThreadPoolExecutor(1)
+    fut = ex.submit(genome_cache.genome_text, kind)
+    ex.shutdown(wait=False)
+    return fut
+
+
+def dump_outputs(d, arrays, sample=4_000_000, seed=12345):
+    """--dump-outputs: each array as d/<name>.npy, float64 (the integers here
+    are below 2^53) or, for bytes, float32; an array of more than `sample`
+    elements as a fixed, seeded sample of them in index order"""
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        if hasattr(a, "cpu"):
+            if a.numel() > sample:
+                import torch
+                idx = np.sort(np.random.default_rng(seed).integers(0, a.numel(), size=sample))
+                a = a.reshape(-1).index_select(0, torch.from_numpy(idx).to(a.device))
+            a = a.cpu().numpy()
+        a = np.asarray(a)
+        np.save(os.path.join(d, name + ".npy"),
+                a.astype(np.float32 if a.dtype.itemsize == 1 else np.float64))
+    log("outputs written to %s: %s" % (d, ", ".join(sorted(arrays))))
 
 
 def chrom_sizes_of(contigs):
@@ -306,10 +341,11 @@ def c2_line(args, dix, contigs, dev, oix, mp, steps=20, warmup=3, batch=None):
     return res
 
 
-def c5_scan(args, dix, contigs, cfg_bins, world, rank, dev, dist, oix=None, reps=3):
+def c5_scan(args, dix, contigs, cfg_bins, world, rank, dev, dist, oix=None, reps=3, dump=None):
     """C5 on the resident index: map.bin bytes of every forward base (longSA::
     show) + unique 36-mer counts per contig and per bin, bases split into
-    `world` contiguous ranges, counts all-reduced.  Returns (json, per-rep s)."""
+    `world` contiguous ranges, counts all-reduced.  Returns (json, per-rep s).
+    dump: a directory for the last rep's outputs (dump_outputs), rank 0."""
     import torch
     import smashgpu as S
     starts = bin_starts_for(dict(bins=cfg_bins), contigs, tempfile.mkdtemp())
@@ -380,6 +416,8 @@ def c5_scan(args, dix, contigs, cfg_bins, world, rank, dev, dist, oix=None, reps
     dmap = S.device_view(dix.info.d_map, dix.info.map_bytes, torch.uint8)
     same_map = bool(torch.equal(out, dmap[2 + 2 * g0:2 + 2 * g1]))
     n_uniq = int(cc.sum().item())
+    if dump and rank == 0:
+        dump_outputs(dump, {"bin_counts": bc, "contig_counts": cc, "map_bytes": out})
     value = total * reps / el
     # the bytes the step streams: the rebuild reads all of SA (idx_bytes per
     # rank) and the LCP bytes (1 B), and per position of the window writes +
@@ -462,18 +500,17 @@ def bench_c5(args, cfg, world, rank, local, dist):
     """--config c5: the C5 scan as the headline line."""
     import torch
     import smashgpu as S
-    import synth
     dev = torch.device("cuda", local)
-    contigs = synth.make_genome(cfg["genome"])
-    T, sp, sz, names = S.text_from_contigs(contigs)
+    contigs, (T, sp, sz, names) = args.genome.result()
     dix = S.Index.create(T, sp, sz, names, device=local)
     log("device index: %.1f s, %.1f GB in HBM" % (dix.info.build_seconds,
                                                   dix.info.device_bytes / 1e9))
     oix = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         import oracle as O
         oix, _ = host_index(S, O, dix, T, sp, sz, names)
-    r = c5_scan(args, dix, contigs, cfg["bins"], world, rank, dev, dist, oix, reps=args.steps)
+    r = c5_scan(args, dix, contigs, cfg["bins"], world, rank, dev, dist, oix, reps=args.steps,
+                dump=args.dump_outputs)
     out_j = {"metric": r.pop("metric"), "value": r.pop("value"), "unit": "bases/s",
              "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
              "ms_per_step": r.pop("ms_per_scan"), "higher_is_better": True,
@@ -492,7 +529,7 @@ def bench_c5(args, cfg, world, rank, local, dist):
 
 
 def mem_line(args, cfg, dix, d_reads, n, dev, oix, world=1, rank=0, dist=None, steps=None,
-             warmup=None, cpu_seconds=None):
+             warmup=None, cpu_seconds=None, dump=None):
     """MEM (-maxmatch) of n C3-style reads (d_reads: dense [n, L] on the
     device; csrc/mem.hip, smash_match_batch SMASH_MODE_MEM), every launch over
     all of them; roofline from the line transitions of mem.hip's own probe
@@ -541,6 +578,8 @@ def mem_line(args, cfg, dix, d_reads, n, dev, oix, world=1, rank=0, dist=None, s
         el = float(t.item())
     kms = sum(ev[2 * i].elapsed_time(ev[2 * i + 1]) for i in range(steps)) / steps
     counts = nn.cpu().numpy()
+    if dump and rank == 0:
+        dump_outputs(dump, {"mem_counts": counts})
     value = n * world * steps / el
     log("MEM: %d reads x %d launches in %.3f s -> %.3e reads/s; %.1f ms per launch; %.1f MEMs "
         "per read (max %d, cap %d)" % (n, steps, el, value, kms, counts.mean(), counts.max(), cap))
@@ -621,24 +660,23 @@ def bench_mem(args, cfg, world, rank, local, dist):
     its own (cfg pairs, seeded as C3's)."""
     import torch
     import smashgpu as S
-    import synth
     import readgen
     import oracle as O
     dev = torch.device("cuda", local)
-    contigs = synth.make_genome(cfg["genome"])
-    T, sp, sz, names = S.text_from_contigs(contigs)
+    contigs, (T, sp, sz, names) = args.genome.result()
     dix = S.Index.create(T, sp, sz, names, device=local)
     log("device index: %.1f s" % dix.info.build_seconds)
     P = cfg["pairs"]
     d_reads = readgen.Generator(dix, contigs, cfg["read_len"],
                                 seed=cfg["seed"] * 1000 + rank).generate(P)
     oix = None
-    if rank == 0:
+    if args.full and rank == 0:
         t2 = time.time()
         oix, _ = host_index(S, O, dix, T, sp, sz, names,
                             sample_reads=d_reads[:2000].cpu().numpy())
         log("host copy of the index: %.1f s" % (time.time() - t2))
-    res = mem_line(args, cfg, dix, d_reads, 2 * P, dev, oix, world, rank, dist)
+    res = mem_line(args, cfg, dix, d_reads, 2 * P, dev, oix, world, rank, dist,
+                   dump=args.dump_outputs)
     if rank == 0:
         print(json.dumps(res), flush=True)
     if world > 1:
@@ -811,6 +849,12 @@ def main():
                     help="skip the C2 and MEM lines on the same index (c3, one GPU)")
     ap.add_argument("--feed-pairs", type=int, default=0,
                     help="pairs of the file-fed run (0: all the rank's pairs, the C3 run)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also the roofline, the CPU baselines and oracle "
+                         "comparisons, the file-fed run and the C2 / MEM / C5 lines on the same "
+                         "index (the --no-* options choose among these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy")
     args = ap.parse_args()
     cfg = dict(CONFIGS[args.config])
     if args.pairs:
@@ -818,9 +862,10 @@ def main():
     if args.batch:
         cfg["batch"] = args.batch
 
+    t0 = time.time()
+    args.genome = genome_start(cfg["genome"])
     import torch
     import smashgpu as S
-    import synth
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -841,9 +886,7 @@ def main():
     if args.config == "c3mem":
         return bench_mem(args, cfg, world, rank, local, dist)
 
-    t0 = time.time()
-    contigs = synth.make_genome(cfg["genome"])
-    T, sp, sz, names = S.text_from_contigs(contigs)
+    contigs, (T, sp, sz, names) = args.genome.result()
     log("genome %s: %.3f Gbp, N=%d (%.1fs)" % (cfg["genome"], sum(len(s) for _, s in contigs) / 1e9,
                                                len(T), time.time() - t0))
     dix = S.Index.create(T, sp, sz, names, device=local)
@@ -1006,7 +1049,22 @@ def main():
                    if sharded else "single GPU",
                    "index_build_s": round(dix.info.build_seconds, 2),
                    "index_hbm_gb": round(dix.info.device_bytes / 1e9, 2)},
+        "full": bool(args.full),
     }
+    if args.dump_outputs and rank == 0:
+        # what a caller of the step holds after it: the bin counts (all
+        # ranks', reduced) and the run's counters
+        dump_outputs(args.dump_outputs,
+                     {"counts": counts,
+                      "stats": np.array([v for k, v in st.as_dict().items() if k != "error"])})
+    if not args.full:
+        out["deterministic_counts"] = same
+        out["stats_last_step"] = st.as_dict()
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if sharded:
+            dist.destroy_process_group()
+        return
 
     # ---- roofline + cpu baseline (rank 0) -------------------------------------
     avg_ms = mam_ms / max(launches, 1)

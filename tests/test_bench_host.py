@@ -1,4 +1,4 @@
-"""bench.py's host-side choices (no GPU): the batch chooser."""
+"""bench.py's host-side choices (no GPU): the batch chooser, the output dump."""
 import importlib.util
 import os
 
@@ -41,3 +41,23 @@ def test_fit_batch_respects_the_library_batch_bound():
     b = fit(P, P, 250, 10_000 * GB, max_batch=mb)
     assert b <= mb and b == -(-P // -(-P // b))
     assert fit(12_500_000, P, 150, 10_000 * GB, max_batch=((1 << 32) - 1) // 262) == 12_500_000
+
+
+def test_dump_outputs_writes_float_arrays_and_a_fixed_sample(tmp_path):
+    """--dump-outputs: float64 .npy of integer arrays, float32 of bytes; an
+    array above the sample size as the same seeded sample every time."""
+    import numpy as np
+    import torch
+    dump = _bench().dump_outputs
+    counts = torch.arange(1000, dtype=torch.int64) * 3
+    big = (torch.arange(100_000, dtype=torch.int64) % 251).to(torch.uint8)
+    for d in ("a", "b"):
+        dump(str(tmp_path / d), {"counts": counts, "stats": np.array([1, 2, 1 << 40]),
+                                 "big": big}, sample=5000)
+    a = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in ("counts", "stats", "big")}
+    assert a["counts"].dtype == np.float64 and a["counts"].tolist() == (counts.numpy()).tolist()
+    assert a["stats"].dtype == np.float64 and a["stats"].tolist() == [1, 2, 1 << 40]
+    assert a["big"].dtype == np.float32 and a["big"].shape == (5000,)
+    assert set(a["big"].tolist()) <= set(range(251)) and len(set(a["big"].tolist())) > 200
+    for n in a:
+        assert np.array_equal(a[n], np.load(tmp_path / "b" / (n + ".npy")))
