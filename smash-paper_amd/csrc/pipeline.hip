@@ -33,11 +33,10 @@ enum Stat { S_PAIRS, S_KEYPAIRS, S_DUPEPAIRS, S_POS, S_DUPS, S_KEPT, S_MATCHES, 
 // reduction (a kernel with LDS cannot share a CU with the search, whose
 // blocks hold all of it); the host sums the rows.  S_ERR lives in row 0.
 constexpr uint32_t kStatStride = 16, kStatStripes = 16, kStatWords = kStatStride * kStatStripes;
-// the multi-GPU export's header per key (smash_phase_export): {hash hi, hash
-// lo, nk << 40 | word offset in the owner's segment} = SMASH_EXPORT_HDR_WORDS
-// (round 3 also sent the global pair index and kept nk and the offset in
-// words of their own: 40 B per key, now 24)
-constexpr uint32_t kHdrWords = 1;   // nk << 40 | word offset (round 5: the hashes are recomputed)
+// the multi-GPU export's header per key (smash_phase_export): nk << 40 | word
+// offset in the owner's segment = SMASH_EXPORT_HDR_WORDS (the hashes are
+// recomputed by the owner: 8 B per key)
+constexpr uint32_t kHdrWords = 1;
 constexpr uint64_t kHdrOffMask = (uint64_t(1) << 40) - 1;
 static_assert(kHdrWords == SMASH_EXPORT_HDR_WORDS, "smash_gpu.h's export header");
 }  // namespace
@@ -109,7 +108,7 @@ struct smash_pipeline {
   uint8_t *d_keep = nullptr;
   uint64_t *d_slot = nullptr;     // [max_pairs] k_dedup_claim -> k_dedup_decide
   uint8_t *d_contest = nullptr;   // [max_pairs] claims of an already-claimed key mark it
-                                  // (kSlotIns; null: SMASH_CLAIM_FLAG=0, every decide reads)
+                                  // (kSlotIns)
   uint64_t *d_tsum = nullptr;     // [tiles] the LDS-free scans' tile aggregates / prefixes
   int64_t *d_tlast = nullptr;
   bool cnt_ready = false;         // k_dedup_decide wrote d_cnt / d_lp for this batch
@@ -142,8 +141,6 @@ struct smash_pipeline {
   bool fused_bin = true;
   uint32_t bin_flush = 0x8000;    // k_emit_bin_lds's 16-bit counter flush threshold
   uint32_t *d_binpart = nullptr;  // [kBinBlocks][nbins]: k_emit_bin_lds's per-block counts
-  uint32_t coop_copy = 7;         // wave-cooperative key-word copies, bit 0: export, 1: single-GPU
-                                  // decide, 2: owner decide (SMASH_COOP_COPY=0: per lane)
   bool bin_lds = true;            // k_emit_bin_lds when the bins fit (SMASH_BIN_LDS=0: global
                                   // atomics; the LDS form runs in the gap SMASH_GATE_POST leaves)
   bool pos_dirty = false;         // the positions arrays are not materialised yet
@@ -763,307 +760,6 @@ __global__ __launch_bounds__(kB) void k_post_fast(PostCfg c, const uint64_t *__r
   post_stats(nm, np, err, stats);
 }
 
-// The persistent pair-key set of smashMEM.py:149,217-228 (dupeSet), exact:
-// a key is the pair's kept hit list (tid << 48 | pos0 per hit, r1 then r2 in
-// HI order, smashMEM.py:122-131).  Open addressing on the 64-bit hash `hi`;
-// slot = {hi, ref}, ref = epoch << 40 | (1 + arena offset of the key record
-// [lo, nk, words]) (0: the inserting thread has not published it yet).  A
-// hash match counts as the same key only when lo, nk and every hit word
-// agree, so a hash collision is a different key (it goes on probing), never a
-// false duplicate.
-//
-// Slot accesses are relaxed, with no per-key release / acquire (agent-scope
-// fences write back / invalidate the XCD's L2 on gfx950 and made the round-2
-// insert kernel 5 ms per 2 M pairs): a launch compares only against records
-// of earlier launches, which are visible across the kernel boundary, and
-// against this launch's claims through the claimers' own input rows (the
-// claim / decide kernels below).  Epochs wrap after 2^24 launches.
-constexpr int kRefShift = 40;
-// a published ref (the key's record is in the arena) carries kRefPub; the
-// in-batch claims of k_dedup_claim (pair index + 1, this epoch) do not
-constexpr uint64_t kRefPub = 1ull << 39;
-struct KeyRef {
-  const uint64_t *w;   // the key's hit words
-  uint32_t nk;
-  uint64_t lo;
-};
-
-__device__ bool same_key(const uint64_t *rec, const KeyRef &k) {
-  if (rec[0] != k.lo || rec[1] != k.nk) return false;
-  for (uint32_t i = 0; i < k.nk; ++i)
-    if (rec[2 + i] != k.w[i]) return false;
-  return true;
-}
-
-__device__ bool same_key(const KeyRef &a, const KeyRef &b) {
-  if (a.lo != b.lo || a.nk != b.nk) return false;
-  for (uint32_t i = 0; i < a.nk; ++i)
-    if (a.w[i] != b.w[i]) return false;
-  return true;
-}
-
-// the wave's inclusive prefix of v (every lane calls it) and its total
-__device__ __forceinline__ uint32_t wave_incl(uint32_t v, uint32_t &total) {
-  const uint32_t lane = threadIdx.x & 63;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t y = __shfl_up(v, d, 64);
-    if (lane >= uint32_t(d)) v += y;
-  }
-  total = __shfl(v, 63, 64);
-  return v;
-}
-
-// the decide kernels take kDecGroups groups of 64 consecutive keys per wave
-// per trip and reserve their arena space with ONE atomic: the arena top is a
-// single address, and one atomic per 64 keys (~100 k per 6.25 M-pair batch)
-// serialised on its L2 channel for ~1 ms
-constexpr uint32_t kDecGroups = 4;
-
-// The key records {hash lo, nk, hit words} of a wave's winners, written by
-// the whole wave: the decide kernels give each group of 64 keys one
-// contiguous arena range
-// (lane l's record at off(l), incl = the inclusive prefix of the record
-// sizes), so word t of the range belongs to the first lane l with
-// incl(l) > t and consecutive lanes store consecutive words (a lane-per-record
-// loop stores 64 words a record apart per instruction).  ok: the lane's
-// record fits the arena; lo / m / src: its hash lo, word count and words.
-// Every lane of the wave calls it (wave-uniform trip count).
-__device__ __forceinline__ void wave_fill_records(uint64_t *arena, uint64_t off, uint32_t incl,
-                                                  uint32_t total, bool ok, uint64_t lo, uint32_t m,
-                                                  const uint64_t *src, bool coop) {
-  if (!coop) {   // (SMASH_COOP_COPY=0: one record per lane, the round-3 form)
-    if (ok) {
-      uint64_t *rec = arena + off;
-      rec[0] = lo;
-      rec[1] = m;
-      for (uint32_t j = 0; j < m; ++j) rec[2 + j] = src[j];
-    }
-    return;
-  }
-  const uint32_t lane = threadIdx.x & 63;
-  const uint64_t srcv = reinterpret_cast<uint64_t>(src);
-  for (uint32_t t0 = 0; t0 < total; t0 += 64) {
-    const uint32_t t = t0 + lane;
-    uint32_t l = 0;
-#pragma unroll
-    for (uint32_t step = 32; step; step >>= 1)
-      if (uint32_t(__shfl(int(incl), int(l + step - 1), 64)) <= t) l += step;
-    l = l < 63u ? l : 63u;
-    // (the shuffle runs on every lane, outside the select: a cross-lane read
-    // under a partial exec mask returns 0 from the lanes it excludes)
-    const uint32_t prev = uint32_t(__shfl(int(incl), int((l + 63u) & 63u), 64));
-    const uint32_t before = l ? prev : 0u;
-    const uint32_t r = t - before;   // word r of lane l's record
-    const bool lok = __shfl(int(ok), int(l), 64) != 0;
-    const uint64_t loff = __shfl(off, int(l), 64), llo = __shfl(lo, int(l), 64);
-    const uint32_t lm = uint32_t(__shfl(int(m), int(l), 64));
-    const uint64_t *ls = reinterpret_cast<const uint64_t *>(__shfl(srcv, int(l), 64));
-    if (t < total && lok) arena[loff + r] = r == 0 ? llo : r == 1 ? uint64_t(lm) : ls[r - 2];
-  }
-}
-
-// ---------------------------------------------------------------------------
-// Single-GPU de-dup without a sort (the pair-key set of smashMEM.py:149,
-// 217-228, first occurrence in pair order wins): two kernels, no LDS, so they
-// run beside the next batch's search.
-//
-// k_dedup_claim: every keyed pair q walks the probe sequence of its hash hi.
-//   * an empty slot: CAS the hi in, then publish ref = epoch << 40 | (q + 1),
-//     a claim of this batch;
-//   * a slot holding hi whose ref is published (kRefPub, an earlier batch's
-//     key): same key (record words compared) -> q is a duplicate of an
-//     earlier batch; else go on probing (a hash collision);
-//   * a slot holding hi claimed in this batch (this epoch, no kRefPub) by pair
-//     q2: same key (q2's hit row compared) -> atomicMin the ref with
-//     epoch << 40 | (q + 1): the slot ends up naming the smallest pair of the
-//     batch with that key; else go on probing.
-//   A slot's key never changes once claimed (every pair that lowers its ref
-//   has the claimer's key), so a comparison against whichever pair the ref
-//   names is a comparison against the claimer.  A claim's ref is stored right
-//   after its CAS; a prober that sees the hi before the ref reads the slot
-//   again on its next trip.
-// k_dedup_decide: pair q is kept iff its slot's ref is still its own claim
-//   (the smallest pair of its key in the batch, and the key is new); the
-//   kept pair writes the key's record into the arena and publishes the ref
-//   (kRefPub: never equal to a claim, so the other pairs of the slot, reading
-//   it before or after, all lose).  Fused: k_count_last's per-pair count and
-//   last position.
-// slot_of[q]: the claimed slot, kSlotOld (a key of an earlier batch) or
-// kSlotNone (no key, or the set is full: the error is raised).
-// ---------------------------------------------------------------------------
-constexpr uint64_t kSlotOld = ~0ull, kSlotNone = ~0ull - 1;
-// (single GPU) slot_of flag: the pair's claim filled an empty slot.  Unless
-// a later claim of the same key marked it (contest[q]), nobody else claimed
-// that slot this batch, so the pair wins and k_dedup_decide skips re-reading
-// the slot (one random table line per key).  Every later claimant marks the
-// claim it finds (the slot's current minimum), and the first of them finds
-// the filler, so a filler that lost is always marked.
-constexpr uint64_t kSlotIns = 1ull << 62;
-
-__device__ __forceinline__ KeyRef pair_key(const HitRows &hits, const int32_t *nk,
-                                           const uint64_t *hash, uint64_t q) {
-  const int32_t k = nk[q];
-  return KeyRef{hits.row(q, k), uint32_t(k), hash[2 * q + 1]};
-}
-
-__global__ void k_dedup_claim(const int32_t *__restrict__ nk, const uint64_t *__restrict__ hash,
-                              HitRows hits, uint64_t n,
-                              uint64_t *table, uint64_t mask, const uint64_t *arena,
-                              uint64_t epoch, uint64_t *slot_of, uint8_t *contest,
-                              unsigned long long *stats) {
-  SMASH_BESIDE_SEARCH();
-  const uint64_t stride = uint64_t(gridDim.x) * blockDim.x;
-  int32_t err = 0;
-  for (uint64_t q = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; q < n; q += stride) {
-    if (nk[q] < 0) continue;
-    const KeyRef me = pair_key(hits, nk, hash, q);
-    const uint64_t hi = hash[2 * q];
-    const unsigned long long mine = (epoch << kRefShift) | (q + 1);
-    uint64_t res = kSlotNone;
-    uint64_t i = (hi ^ (hi >> 31)) & mask;
-    uint32_t waits = 0;
-    for (uint64_t probe = 0; probe <= mask;) {
-      unsigned long long *sh = reinterpret_cast<unsigned long long *>(&table[2 * i]);
-      unsigned long long *sr = sh + 1;
-      unsigned long long cur = __hip_atomic_load(sh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (cur == 0) {
-        const unsigned long long prev = atomicCAS(sh, 0ull, (unsigned long long)hi);
-        if (prev == 0) {
-          __hip_atomic_store(sr, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          res = i | (contest ? kSlotIns : 0ull);
-          break;
-        }
-        cur = prev;
-      }
-      if (cur == hi) {
-        const unsigned long long ref =
-            __hip_atomic_load(sr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (ref == 0) {
-          // the claimer is between its CAS and its ref store: read this slot
-          // again next trip (no wait inside the trip: a claimer in this wave
-          // may be laid out after this branch)
-          if (++waits > (1u << 22)) {   // (not a reachable state)
-            err = SMASH_ERR_UNSUPPORTED;
-            break;
-          }
-          continue;
-        }
-        if (ref & kRefPub) {
-          if ((ref >> kRefShift) != epoch &&
-              same_key(arena + ((ref & (kRefPub - 1)) - 1), me)) {
-            res = kSlotOld;
-            break;
-          }
-        } else if ((ref >> kRefShift) == epoch) {
-          const uint64_t q2 = (ref & (kRefPub - 1)) - 1;
-          if (same_key(me, pair_key(hits, nk, hash, q2))) {
-            if (contest) contest[q2] = 1;   // (see kSlotIns)
-            atomicMin(sr, mine);
-            res = i;
-            break;
-          }
-        }
-        // (an unpublished ref of an earlier epoch: its batch ran out of
-        // arena, an error already raised; no record to compare)
-      }
-      ++probe;
-      i = (i + 1) & mask;
-    }
-    if (res == kSlotNone && err == 0) err = SMASH_ERR_NOMEM;   // the set is full
-    slot_of[q] = res;
-  }
-  if (err) atomicCAS(&stats[S_ERR], 0ull, (unsigned long long)(unsigned)err);
-}
-
-// one wave per kDecGroups x 64 consecutive pairs per trip (wave-wide scans)
-__global__ void k_dedup_decide(const int32_t *__restrict__ nk, const uint64_t *__restrict__ hash,
-                               HitRows hits,
-                               const uint32_t *__restrict__ nmajor,
-                               const int64_t *__restrict__ chrom_off, uint64_t n,
-                               uint64_t *table, uint64_t *arena, uint64_t arena_cap,
-                               unsigned long long *arena_top, uint64_t epoch,
-                               const uint64_t *__restrict__ slot_of,
-                               const uint8_t *__restrict__ contest, uint8_t *keep,
-                               uint32_t *cnt, int64_t *lp, unsigned long long *stats, bool coop) {
-  SMASH_BESIDE_SEARCH();
-  const uint64_t stride = uint64_t(gridDim.x) * blockDim.x;
-  unsigned long long kp = 0, dp = 0;
-  bool full = false;
-  const uint32_t lane = threadIdx.x & 63;
-  for (uint64_t b0 = (uint64_t(blockIdx.x) * blockDim.x + (threadIdx.x & ~63u)) * kDecGroups;
-       b0 < n; b0 += stride * kDecGroups) {
-    bool wins[kDecGroups];
-    uint32_t needs[kDecGroups], incls[kDecGroups], tots[kDecGroups];
-    uint32_t sum = 0;
-#pragma unroll
-    for (uint32_t g = 0; g < kDecGroups; ++g) {
-      const uint64_t q = b0 + 64 * g + lane;
-      const int32_t m = q < n ? nk[q] : -1;
-      bool win = false;
-      if (m >= 0) {
-        const uint64_t sl = slot_of[q];
-        if (sl < kSlotNone && (sl & kSlotIns) && !contest[q]) {
-          win = true;                       // the slot's only claimant this batch
-        } else if (sl < kSlotNone) {
-          const unsigned long long ref = __hip_atomic_load(
-              reinterpret_cast<unsigned long long *>(&table[2 * (sl & ~kSlotIns) + 1]),
-              __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          win = ref == ((epoch << kRefShift) | (q + 1));
-        }
-        ++kp;
-        dp += win ? 0 : 1;
-      }
-      wins[g] = win;
-      needs[g] = win ? 2u + uint32_t(m) : 0u;
-      incls[g] = wave_incl(needs[g], tots[g]);
-      sum += tots[g];
-    }
-    unsigned long long wbase = 0;
-    if (lane == 63 && sum) wbase = atomicAdd(arena_top, (unsigned long long)sum);
-    wbase = __shfl(wbase, 63, 64);
-#pragma unroll
-    for (uint32_t g = 0; g < kDecGroups; ++g) {
-      const uint64_t q = b0 + 64 * g + lane;
-      const bool in = q < n;
-      const int32_t m = in ? nk[q] : -1;
-      const bool win = wins[g];
-      const uint32_t need = needs[g], incl = incls[g], total = tots[g];
-      const uint64_t off = uint64_t(wbase) + incl - need;
-      wbase += total;
-      const bool ok = win && off + need <= arena_cap;
-      wave_fill_records(arena, off, incl, total, ok, win ? hash[2 * q + 1] : 0ull,
-                        win ? uint32_t(m) : 0u, hits.row(in ? q : 0, m), coop);
-      if (win) {
-        if (!ok) {
-          full = true;   // the slot stays a claim: never matched (no kRefPub)
-        } else {
-          __hip_atomic_store(
-              reinterpret_cast<unsigned long long *>(&table[2 * (slot_of[q] & ~kSlotIns) + 1]),
-              (unsigned long long)((epoch << kRefShift) | kRefPub | (off + 1)), __ATOMIC_RELAXED,
-              __HIP_MEMORY_SCOPE_AGENT);
-        }
-      }
-      if (in) {
-        keep[q] = win ? 1 : 0;
-        const uint32_t c = win ? nmajor[q] : 0;   // k_count_last
-        cnt[q] = c;
-        int64_t last = -1;
-        if (c) {
-          const uint64_t *h = hits.row(q, m);
-          for (int32_t j = m - 1; j >= 0; --j)
-            if (chrom_off[uint32_t(h[j] >> 48)] >= 0) {
-              last = int64_t(h[j] & 0xFFFFFFFFFFFFull);
-              break;
-            }
-        }
-        lp[q] = last;
-      }
-    }
-  }
-  wave_stats(stats, S_KEYPAIRS, kp, S_DUPEPAIRS, dp, full ? SMASH_ERR_NOMEM : 0);
-}
-
 // ---------------------------------------------------------------------------
 // The two scans of the fused positions path without LDS (hipcub's use LDS and
 // a decoupled look-back): per pair cnt (u32, inclusive sum -> posoff[q + 1])
@@ -1568,19 +1264,10 @@ HitRows hit_rows(const smash_pipeline *p) { return HitRows{p->d_hhead, p->d_hits
 }  // namespace
 }  // namespace smash
 
-using namespace smash;
+// the pair-key set: its format, the claim / decide kernels, its growth
+#include "keyset.hpp"
 
-// table slots and arena words for a key set of `keys` keys (at least the
-// batch's max_pairs): 2x the keys in power-of-two slots, 16 words per key
-static void key_set_geometry(uint64_t keys, uint64_t max_pairs, uint64_t *slots,
-                             uint64_t *arena_words) {
-  const uint64_t cap = 2 * std::max<uint64_t>(keys, max_pairs);
-  uint64_t pw = 1;
-  while (pw < cap) pw <<= 1;
-  *slots = pw;
-  *arena_words = std::min<uint64_t>(16 * std::max<uint64_t>(keys, max_pairs) + (1u << 20),
-                                    kRefPub - 2);
-}
+using namespace smash;
 
 extern "C" uint64_t smash_pipeline_max_batch(uint32_t read_len, uint32_t min_len) {
   if (read_len == 0 || read_len > 255 || min_len < 2 || read_len < min_len) return 0;
@@ -1772,8 +1459,6 @@ extern "C" int smash_pipeline_create(const smash_index *ix,
       const char *fl = getenv("SMASH_BIN_FLUSH");
       const unsigned long f = fl ? std::strtoul(fl, nullptr, 10) : 0;
       if (f >= 2 && f <= 0x8000 && !(f & (f - 1))) p->bin_flush = uint32_t(f);
-      const char *cc = getenv("SMASH_COOP_COPY");
-      if (cc) p->coop_copy = uint32_t(std::strtoul(cc, nullptr, 10)) & 7u;
       auto on = [](const char *v, bool dflt) {
         const char *x = getenv(v);
         return x && x[0] ? x[0] == '1' : dflt;
@@ -1791,10 +1476,7 @@ extern "C" int smash_pipeline_create(const smash_index *ix,
     p->d_stats = dalloc<unsigned long long>(kStatWords);
     SMASH_HIPX(hipMemset(p->d_stats, 0, 8 * kStatWords));
     p->d_slot = dalloc<uint64_t>(P);
-    {
-      const char *cf = getenv("SMASH_CLAIM_FLAG");   // (A/B: 0 = every decide reads its slot)
-      if (!(cf && cf[0] == '0')) p->d_contest = dalloc<uint8_t>(P);
-    }
+    p->d_contest = dalloc<uint8_t>(P);
     p->d_tsum = dalloc<uint64_t>(P / kScanTile + 1);
     p->d_tlast = dalloc<int64_t>(P / kScanTile + 1);
     p->d_send_q = dalloc<uint32_t>(P);
@@ -2024,19 +1706,13 @@ extern "C" int smash_phase_search_ahead(smash_pipeline *p, const uint8_t *d_read
   return search_into(p, k, d_reads, n_pairs, p->ev_in);
 }
 
-// 1 .. 2^24 - 1, never 0 (an unpublished slot)
-static uint64_t next_epoch(smash_pipeline *p) {
-  p->epoch = p->epoch % ((1ull << (64 - smash::kRefShift)) - 1) + 1;
-  return p->epoch;
-}
-
 // single GPU: the persistent set, first occurrence in pair order
 // (k_dedup_claim, k_dedup_decide), and the positions' per-pair counts
 static int dedup_local(smash_pipeline *p, hipStream_t s) {
   const uint64_t n = p->n_pairs;
   if (!n) return SMASH_OK;
   const uint64_t epoch = next_epoch(p);
-  if (p->d_contest) SMASH_HIP(hipMemsetAsync(p->d_contest, 0, n, s));
+  SMASH_HIP(hipMemsetAsync(p->d_contest, 0, n, s));
   k_dedup_claim<<<grid_for(n, kB, 8192), kB, 0, s>>>(p->d_nk, p->d_hash, hit_rows(p), n,
                                                      p->d_table, p->table_mask, p->d_arena, epoch,
                                                      p->d_slot, p->d_contest, p->d_stats);
@@ -2044,7 +1720,7 @@ static int dedup_local(smash_pipeline *p, hipStream_t s) {
   k_dedup_decide<<<grid_for((n + kDecGroups - 1) / kDecGroups, kB, 8192), kB, 0, s>>>(
       p->d_nk, p->d_hash, hit_rows(p), p->d_nmajor, p->d_chrom_off, n, p->d_table,
       p->d_arena, p->arena_cap, p->d_arena_top, epoch, p->d_slot, p->d_contest, p->d_keep,
-      p->d_cnt, p->d_lp, p->d_stats, (p->coop_copy & 2u) != 0);
+      p->d_cnt, p->d_lp, p->d_stats);
   SMASH_HIP(hipGetLastError());
   p->cnt_ready = true;
   return SMASH_OK;
@@ -2205,10 +1881,10 @@ extern "C" int smash_count_batches_ready(smash_pipeline *p, const uint8_t *d_rea
 
 // ---- multi-GPU de-dup exchange ------------------------------------------------
 // Each rank exports its keyed pairs to owner = (hash hi >> 1) % world: a
-// 3-word header {hi, lo, nk << 40 | word offset} per key and the
-// key's nk hit words (hash + canonical key bytes + index).
-// The owner decides first-wins over the exact keys and answers one byte per
-// header.
+// one-word header nk << 40 | word offset per key (kHdrWords) and the key's nk
+// hit words; the owner recomputes the hashes from the words (key_hashes).
+// The owner decides first-wins over the exact keys (keyset.hpp) and answers
+// one byte per header.
 namespace smash {
 namespace {
 // the owner rank of a key: its hash hi without bit 0, which is always set
@@ -2257,13 +1933,8 @@ __device__ __forceinline__ WaveGroup wave_owner_groups(bool act, uint32_t ow, ui
     const uint32_t o = uint32_t(__shfl(int(ow), leader, 64));
     const bool in = act && ow == o;
     const uint64_t same = __ballot(in);
-    uint32_t x = in ? k : 0u;   // inclusive scan of the group's word counts
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t y = __shfl_up(x, d, 64);
-      if (lane >= uint32_t(d)) x += y;
-    }
-    const uint32_t wsum = __shfl(x, 63, 64);
+    uint32_t wsum;   // inclusive scan of the group's word counts
+    const uint32_t x = wave_incl(in ? k : 0u, wsum);
     if (lane == uint32_t(leader)) {
       s_e[o] = uint32_t(__popcll(same));
       s_w[o] = wsum;
@@ -2316,9 +1987,9 @@ __global__ void k_export_totals(const uint64_t *bc, const uint64_t *boff, int wo
 __global__ __launch_bounds__(kB) void k_export_fill(const int32_t *nk, const uint64_t *hash,
                                                     HitRows hits,
                                                     uint64_t n, int world, uint32_t nblk,
-                                                    uint64_t gbase, const uint64_t *boff,
+                                                    const uint64_t *boff,
                                                     uint64_t *hdr, uint64_t *words,
-                                                    uint32_t *send_q, bool coop) {
+                                                    uint32_t *send_q) {
   __shared__ uint32_t s_e[kExWaves][64], s_w[kExWaves][64];
   const uint32_t wv = threadIdx.x >> 6;
   for (uint32_t o = threadIdx.x; o < kExWaves * 64; o += blockDim.x) {
@@ -2344,207 +2015,29 @@ __global__ __launch_bounds__(kB) void k_export_fill(const int32_t *nk, const uin
     const uint64_t seg_w = boff[uint64_t(ow) * nblk] & 0xFFFFFFFFull;   // owner's word segment
     e += bo >> 32;
     w += bo & 0xFFFFFFFFull;
-    (void)gbase;   // the receive order is the global order: no pair index travels
-    // the key's words travel and its hashes do not: the owner recomputes
+    // the receive order is the global order: no pair index travels.  The
+    // key's words travel and its hashes do not: the owner recomputes
     // them from the words (key_hashes), 8 B of header per key instead of 24
     hdr[kHdrWords * e] = uint64_t(k) << 40 | (w - seg_w);   // offset in the owner's words
     send_q[e] = uint32_t(q);
-    if (!coop) {   // (SMASH_COOP_COPY=0: one key per lane, the round-3 form)
-      const uint64_t *src = hits.row(q, int32_t(k));
-      for (uint32_t i = 0; i < k; ++i) words[w + i] = src[i];
-    }
   }
-  if (!coop) return;
   // the keys' words, the wave together: word t of the wave's concatenated
   // key lists (lane order) is word t - pre(l) of lane l's key, so
   // consecutive lanes store consecutive words of an owner's segment (a
   // lane-per-key loop stores 64 scattered words per instruction)
   const uint32_t lane = threadIdx.x & 63;
-  uint32_t incl = k;   // inclusive scan of the word counts over the wave
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t y = __shfl_up(incl, d, 64);
-    if (lane >= uint32_t(d)) incl += y;
-  }
-  const uint32_t total = __shfl(incl, 63, 64);
+  uint32_t total;
+  const uint32_t incl = wave_incl(k, total);   // of the word counts over the wave
   const uint64_t row = act ? reinterpret_cast<uint64_t>(hits.row(q, int32_t(k))) : 0ull;
   for (uint32_t t0 = 0; t0 < total; t0 += 64) {   // (wave-uniform: every shuffle has all lanes)
     const uint32_t t = t0 + lane;
-    // the lane whose key holds word t: the first l with incl(l) > t
-    uint32_t l = 0;
-#pragma unroll
-    for (uint32_t step = 32; step; step >>= 1)
-      if (uint32_t(__shfl(int(incl), int(l + step - 1), 64)) <= t) l += step;
-    l = l < 63u ? l : 63u;   // (t >= total: a lane past the end)
-    // (the shuffle runs on every lane, outside the select: a cross-lane read
-    // under a partial exec mask returns 0 from the lanes it excludes)
-    const uint32_t prev = uint32_t(__shfl(int(incl), int((l + 63u) & 63u), 64));
-    const uint32_t before = l ? prev : 0u;
+    uint32_t before;
+    const uint32_t l = wave_word_owner(incl, t, before);   // the lane whose key holds word t
     const uint64_t wl = __shfl(w, int(l), 64), rl = __shfl(row, int(l), 64);
     if (t < total) words[wl + (t - before)] = reinterpret_cast<const uint64_t *>(rl)[t - before];
   }
 }
 
-// the pair key's two hashes from its hit words, exactly as k_post /
-// k_post_fast fold them while they build the key (a word is tid << 48 | pos0,
-// pos0 < 2^48, so the | there is the ^ here)
-__device__ inline void key_hashes(const uint64_t *w, uint32_t nk, uint64_t mask, uint64_t &hh,
-                                  uint64_t &hl) {
-  hh = 0x9E3779B97F4A7C15ull;
-  hl = 0xD1B54A32D192ED03ull;
-  for (uint32_t i = 0; i < nk; ++i) {
-    const uint64_t x = w[i];
-    hh = mix64(hh ^ x) + 0x632BE59BD9B4E019ull;
-    hl = mix64(hl + x * 0x9E3779B97F4A7C15ull) ^ (hl >> 29);
-  }
-  hh = (mix64(hh ^ uint64_t(nk)) & mask) | 1;
-  hl = (mix64(hl + uint64_t(nk)) & mask) | 1;
-}
-
-// base[0..world]: header prefix per source rank; base[65..65+world]: word
-// prefix per source rank.  hi: the key's hash hi (recomputed, like .lo)
-__device__ __forceinline__ KeyRef recv_key(const uint64_t *recv, const uint64_t *words,
-                                           const uint64_t *base, int world, uint64_t j,
-                                           uint64_t hmask, uint64_t *hi = nullptr) {
-  int r = 0;
-  while (r + 1 < world && j >= base[r + 1]) ++r;
-  const uint64_t nw = recv[kHdrWords * j];
-  KeyRef k{words + base[65 + r] + (nw & kHdrOffMask), uint32_t(nw >> 40), 0};
-  uint64_t h = 0;
-  key_hashes(k.w, k.nk, hmask, h, k.lo);
-  if (hi) *hi = h;
-  return k;
-}
-
-// The owner's first-wins decision, the single-GPU claim / decide scheme
-// (k_dedup_claim / k_dedup_decide) over the received keys: key j claims an
-// empty slot with ref = epoch << 40 | (j + 1), or lowers a same-key claim of
-// this launch with atomicMin (the receive order is the global pair order, so
-// the smallest j is the first pair), or finds the key published by an
-// earlier launch (a duplicate).  k_owner_decide: j is kept iff the slot still
-// holds its own claim; the winner writes the record and publishes it.
-__global__ void k_owner_claim(const uint64_t *recv, const uint64_t *words, const uint64_t *base,
-                              int world, uint64_t n, uint64_t *table, uint64_t mask,
-                              const uint64_t *arena, uint64_t epoch, uint64_t *slot_of,
-                              unsigned long long *stats, uint64_t hmask) {
-  const uint64_t stride = uint64_t(gridDim.x) * blockDim.x;
-  int32_t err = 0;
-  for (uint64_t j = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; j < n; j += stride) {
-    uint64_t hi = 0;
-    const KeyRef me = recv_key(recv, words, base, world, j, hmask, &hi);
-    const unsigned long long mine = (epoch << kRefShift) | (j + 1);
-    uint64_t res = kSlotNone;
-    uint64_t i = (hi ^ (hi >> 31)) & mask;
-    uint32_t waits = 0;
-    for (uint64_t probe = 0; probe <= mask;) {
-      unsigned long long *sh = reinterpret_cast<unsigned long long *>(&table[2 * i]);
-      unsigned long long *sr = sh + 1;
-      unsigned long long cur = __hip_atomic_load(sh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (cur == 0) {
-        const unsigned long long prev = atomicCAS(sh, 0ull, (unsigned long long)hi);
-        if (prev == 0) {
-          __hip_atomic_store(sr, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          res = i;
-          break;
-        }
-        cur = prev;
-      }
-      if (cur == hi) {
-        const unsigned long long ref =
-            __hip_atomic_load(sr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (ref == 0) {   // the claimer is between its CAS and its ref store (k_dedup_claim)
-          if (++waits > (1u << 22)) {
-            err = SMASH_ERR_UNSUPPORTED;
-            break;
-          }
-          continue;
-        }
-        if (ref & kRefPub) {
-          if ((ref >> kRefShift) != epoch &&
-              same_key(arena + ((ref & (kRefPub - 1)) - 1), me)) {
-            res = kSlotOld;
-            break;
-          }
-        } else if ((ref >> kRefShift) == epoch) {
-          const uint64_t j2 = (ref & (kRefPub - 1)) - 1;
-          if (same_key(me, recv_key(recv, words, base, world, j2, hmask))) {
-            atomicMin(sr, mine);
-            res = i;
-            break;
-          }
-        }
-      }
-      ++probe;
-      i = (i + 1) & mask;
-    }
-    if (res == kSlotNone && err == 0) err = SMASH_ERR_NOMEM;   // the set is full
-    slot_of[j] = res;
-  }
-  if (err) atomicCAS(&stats[S_ERR], 0ull, (unsigned long long)(unsigned)err);
-}
-
-__global__ void k_owner_decide(const uint64_t *recv, const uint64_t *words, const uint64_t *base,
-                               int world, uint64_t n, uint64_t *table, uint64_t *arena,
-                               uint64_t arena_cap, unsigned long long *arena_top, uint64_t epoch,
-                               const uint64_t *__restrict__ slot_of, uint8_t *flags,
-                               unsigned long long *stats, bool coop, uint64_t hmask) {
-  const uint64_t stride = uint64_t(gridDim.x) * blockDim.x;
-  bool full = false;
-  const uint32_t lane = threadIdx.x & 63;
-  for (uint64_t c0 = (uint64_t(blockIdx.x) * blockDim.x + (threadIdx.x & ~63u)) * kDecGroups;
-       c0 < n; c0 += stride * kDecGroups) {
-    bool wins[kDecGroups];
-    uint32_t needs[kDecGroups], incls[kDecGroups], tots[kDecGroups];
-    uint32_t sum = 0;
-#pragma unroll
-    for (uint32_t g = 0; g < kDecGroups; ++g) {
-      const uint64_t j = c0 + 64 * g + lane;
-      bool win = false;
-      uint32_t m = 0;
-      if (j < n) {
-        m = uint32_t(recv[kHdrWords * j] >> 40);
-        const uint64_t sl = slot_of[j];
-        if (sl < kSlotNone) {
-          const unsigned long long ref = __hip_atomic_load(
-              reinterpret_cast<unsigned long long *>(&table[2 * sl + 1]), __ATOMIC_RELAXED,
-              __HIP_MEMORY_SCOPE_AGENT);
-          win = ref == ((epoch << kRefShift) | (j + 1));
-        }
-      }
-      wins[g] = win;
-      needs[g] = win ? 2u + m : 0u;
-      incls[g] = wave_incl(needs[g], tots[g]);
-      sum += tots[g];
-    }
-    unsigned long long wbase = 0;
-    if (lane == 63 && sum) wbase = atomicAdd(arena_top, (unsigned long long)sum);
-    wbase = __shfl(wbase, 63, 64);
-#pragma unroll
-    for (uint32_t g = 0; g < kDecGroups; ++g) {
-      const uint64_t j = c0 + 64 * g + lane;
-      const bool win = wins[g];
-      const uint32_t need = needs[g], incl = incls[g], total = tots[g];
-      const uint32_t m = win ? need - 2u : 0u;
-      const uint64_t off = uint64_t(wbase) + incl - need;
-      wbase += total;
-      const bool ok = win && off + need <= arena_cap;
-      KeyRef me{words, 0u, 0ull};
-      if (win) me = recv_key(recv, words, base, world, j, hmask);
-      wave_fill_records(arena, off, incl, total, ok, me.lo, win ? m : 0u, me.w, coop);
-      if (win) {
-        if (!ok) {
-          full = true;   // the slot stays a claim: never matched (no kRefPub)
-        } else {
-          __hip_atomic_store(reinterpret_cast<unsigned long long *>(&table[2 * slot_of[j] + 1]),
-                             (unsigned long long)((epoch << kRefShift) | kRefPub | (off + 1)),
-                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-      }
-      if (j < n) flags[j] = win ? 1 : 0;
-    }
-  }
-  if (full) atomicCAS(&stats[S_ERR], 0ull, (unsigned long long)(unsigned)SMASH_ERR_NOMEM);
-}
 __global__ void k_import(const uint8_t *flags, const uint32_t *send_q, uint64_t n_export,
                          uint8_t *keep) {
   const uint64_t o = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
@@ -2604,8 +2097,7 @@ extern "C" int smash_phase_export(smash_pipeline *p, int world, uint64_t global_
   }
   if (n)
     k_export_fill<<<nblk, kB, 0, s>>>(p->d_nk, p->d_hash, hit_rows(p), n, world, nblk,
-                                      global_base, p->d_boff, p->d_send_hdr, p->d_send_words,
-                                      p->d_send_q, (p->coop_copy & 1u) != 0);
+                                      p->d_boff, p->d_send_hdr, p->d_send_words, p->d_send_q);
   SMASH_HIP(hipGetLastError());
   *d_send = p->d_send_hdr;
   *d_send_words = p->d_send_words;
@@ -2655,8 +2147,7 @@ extern "C" int smash_dedup_owner(smash_pipeline *p, const uint64_t *d_recv, uint
   SMASH_HIP(hipGetLastError());
   k_owner_decide<<<grid_for((n_recv + kDecGroups - 1) / kDecGroups, kB, 8192), kB, 0, s>>>(
       d_recv, d_recv_words, p->d_recv_base, world, n_recv, p->d_table, p->d_arena, p->arena_cap,
-      p->d_arena_top, epoch, p->d_oslot, d_flags, p->d_stats, (p->coop_copy & 4u) != 0,
-      p->hash_mask);
+      p->d_arena_top, epoch, p->d_oslot, d_flags, p->d_stats, p->hash_mask);
   SMASH_HIP(hipGetLastError());
   return SMASH_OK;
 }
@@ -2734,29 +2225,6 @@ extern "C" int smash_pipeline_peek(smash_pipeline *p, int32_t *h_nk, uint8_t *h_
   }
   if (h_hash) SMASH_HIP(hipMemcpy(h_hash, p->d_hash, 16 * n, hipMemcpyDeviceToHost));
   return SMASH_OK;
-}
-
-// Growth of a set that holds keys: every occupied slot {hash hi, ref} of the
-// old table moves to the first empty slot of its probe sequence in the new
-// one (the claim kernels' (hi ^ hi >> 31) & mask, linear).  Between batches
-// every ref is published (an arena offset, copied with the arena), so the
-// keys, their records and the first-wins decisions stay as they were; two
-// keys with one hi take two slots, as they did.
-__global__ void k_rehash(const uint64_t *__restrict__ old, uint64_t old_slots, uint64_t *nt,
-                         uint64_t mask) {
-  const uint64_t stride = uint64_t(gridDim.x) * blockDim.x;
-  for (uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < old_slots; i += stride) {
-    const uint64_t hi = old[2 * i];
-    if (!hi) continue;
-    uint64_t j = (hi ^ (hi >> 31)) & mask;
-    for (uint64_t probe = 0; probe <= mask; ++probe, j = (j + 1) & mask) {
-      unsigned long long *sh = reinterpret_cast<unsigned long long *>(&nt[2 * j]);
-      if (atomicCAS(sh, 0ull, (unsigned long long)hi) == 0ull) {
-        nt[2 * j + 1] = old[2 * i + 1];
-        break;
-      }
-    }
-  }
 }
 
 extern "C" int smash_pipeline_reserve_keys(smash_pipeline *p, uint64_t keys, void *stream) {

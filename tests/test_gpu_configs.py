@@ -594,22 +594,20 @@ def test_c4_back_to_back_runs_cross_search(c4_run, W, per_rank, bits, runs, monk
 def test_c4_real_driver_variants(c4_run, monkeypatch):
     """The W = 8 driver, and one pipeline over 24 batches (the key records
     written by one launch and compared by later ones), with each kernel form
-    the knobs select (SMASH_COOP_COPY=0: per-lane key-word copies instead of
-    the wave-cooperative ones; SMASH_BIN_LDS=0: global bin atomics) == the
+    the knobs select (SMASH_BIN_LDS=0: global bin atomics) == the
     oracle, all reported before the first failure is raised (a failing form
     is then named by the others)."""
     from thread_ranks import run_resident
     dix, cs, starts, d_reads, single, orc = c4_run
     res = {}
-    for name, env in [("coop0", {"SMASH_COOP_COPY": "0"}), ("binglobal", {"SMASH_BIN_LDS": "0"}),
-                      ("default", {})]:
+    for name, env in [("binglobal", {"SMASH_BIN_LDS": "0"}), ("default", {})]:
         for k, v in env.items():
             monkeypatch.setenv(k, v)
         total, st = run_resident(dix, d_reads, 8, 10_000, starts, cs)
         res[name] = (st, bool(np.array_equal(total, orc[0])))
         for k in env:
             monkeypatch.delenv(k)
-    for name, env in [("single_batches", {}), ("single_batches_coop0", {"SMASH_COOP_COPY": "0"})]:
+    for name, env in [("single_batches", {})]:
         for k, v in env.items():
             monkeypatch.setenv(k, v)
         one = S.Pipeline(dix, cs, starts, 150, 10_000, dedup_capacity=C4_PAIRS)

@@ -81,7 +81,7 @@ def test_count_batches_equals_batch_by_batch(gix, batch):
 SCHEDULES = {"default": {},
              # round 3's first form: ev_free after k_post, k_prep_direct
              "post_gate_kpost": {"SMASH_GATE_POST": "0", "SMASH_PREP_LDS": "0"},
-             "one_search": {"SMASH_ONE_SEARCH": "1", "SMASH_PRIO": "0"},
+             "one_search": {"SMASH_ONE_SEARCH": "1"},
              "gate_prep": {"SMASH_GATE_PREP": "1"}}
 
 
@@ -93,7 +93,7 @@ def test_resident_runs_back_to_back(gix, batch, sched, monkeypatch):
     with no synchronisation, each after a reset and a zeroing of its own
     counts: every run's counts == one run of smash_count_batches, under
     each stream schedule (SMASH_GATE_POST / _PREP, SMASH_ONE_SEARCH,
-    SMASH_PREP_LDS, SMASH_PRIO: read at pipeline creation / per launch)."""
+    SMASH_PREP_LDS: read at pipeline creation / per launch)."""
     for k, v in SCHEDULES[sched].items():
         monkeypatch.setenv(k, v)
     reads = interleaved_reads("s150")
@@ -135,6 +135,66 @@ def test_full_key_set_fails_loudly(gix, monkeypatch):
     cs = load_chrom_sizes(gold("tiny_chrom_sizes.txt"))
     with pytest.raises(S.SmashError, match="key set full"):
         run_emulated(gix, reads, 2, 150, 6, starts, cs, True, capacity=150)
+
+
+@pytest.mark.parametrize("bits", [0, 2])
+@pytest.mark.parametrize("batch", [63, 64, 65, 257, 700])
+def test_keep_flags_local_and_owner_equal_host_set(gix, batch, bits, monkeypatch):
+    """Every keyed pair's keep flag == first occurrence of its exact key (the
+    hit words, a host set carried across batches), for the single-GPU claim /
+    decide (count_batch) and for the owner's over the exported keys (the phase
+    calls, world 1).  s100 twice: the first pass has in-batch and cross-batch
+    duplicates, the second makes every keyed pair a duplicate of a published
+    record; batch sizes on either side of the decide kernels' 64-key group
+    and 256-key trip; bits = 2: every probe meets colliding hashes.  s100 has
+    1 991 keyed pairs and 1 972 distinct keys: 2 * 1 991 - 1 972 = 2 010
+    duplicate pairs (the CPU oracle's figures).  An unkeyed pair's keep is
+    not compared: the owner path never writes it."""
+    if bits:
+        monkeypatch.setenv("SMASH_KEY_HASH_BITS", str(bits))
+    once = interleaved_reads("s100")
+    reads = np.ascontiguousarray(np.concatenate([once, once]))
+    n = reads.shape[0] // 2
+    assert n == 4000
+    _, starts = load_bins(gold("tiny_bins.txt"))
+    cs = load_chrom_sizes(gold("tiny_chrom_sizes.txt"))
+    d = torch.from_numpy(reads).cuda()
+
+    def run(owner):
+        pipe = S.Pipeline(gix, cs, starts, reads.shape[1], batch, dedup_capacity=n)
+        pipe.reset()
+        c = torch.zeros(len(starts), dtype=torch.int64, device="cuda")
+        tail = torch.empty(2, dtype=torch.int64, device="cuda")
+        seen, bad = set(), []
+        for b0 in range(0, n, batch):
+            b = min(n, b0 + batch) - b0
+            if owner:
+                pipe.phase_map(d[2 * b0:2 * (b0 + b)], b)
+                hdr, words, cnt, wcnt = pipe.phase_export(1, b0)
+                flags = torch.empty(max(int(cnt.sum()), 1), dtype=torch.uint8, device="cuda")
+                pipe.dedup_owner(hdr.clone(), int(cnt.sum()), words.clone(), cnt, wcnt, flags)
+                pipe.phase_import(flags)
+                pipe.phase_positions(tail)
+                pipe.phase_bin(None, c)
+            else:
+                pipe.count_batch(d[2 * b0:2 * (b0 + b)], b, c)
+            nk, keep, hits = pipe.peek(b)
+            for q in range(b):
+                if nk[q] < 0:
+                    continue
+                key = tuple(hits[q, :nk[q]].tolist())
+                if bool(keep[q]) != (key not in seen):
+                    bad.append((b0 + q, int(keep[q])))
+                seen.add(key)
+        st = pipe.stats(raise_on_error=False)
+        print("owner" if owner else "local", "keys", len(seen), "dupe_pairs", st.dupe_pairs,
+              "error", st.error, "wrong keep", bad[:10])
+        assert not bad, bad[:10]
+        assert st.error == 0
+        assert st.dupe_pairs == 2010
+        return c.cpu().numpy().tolist()
+
+    assert run(False) == run(True)
 
 
 @pytest.mark.parametrize("s", ["s100", "s150"])
