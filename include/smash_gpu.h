@@ -232,7 +232,9 @@ typedef struct smash_pipeline smash_pipeline;
 
 typedef struct {
   uint32_t min_len;          /* MAM minimum length (query.h:129: 20) */
-  uint32_t read_len;         /* fixed mate length of the batches (<= 255) */
+  uint32_t read_len;         /* fixed mate length of the batches (<= 255); in
+                                variable-length mode (smash_pipeline_var_len)
+                                the longest a mate can be */
   uint64_t max_pairs;        /* batch capacity */
   uint32_t n_contig;         /* forward contigs = n_seq / 2 */
   const uint32_t *h_tag_offsets; /* [n_contig] sam_header.txt offsets (u32, chromosomes.h:169-196) */
@@ -425,6 +427,22 @@ int smash_pipeline_reset_ex(smash_pipeline *p, uint32_t flags, void *stream);
  * search set's previous post stage.  Default off: a search waits for the
  * work already on `stream` (the reads' H2D copy of a file-fed batch). */
 int smash_pipeline_reads_resident(smash_pipeline *p, int on);
+/* Variable-length mode (default off: every mate has cfg.read_len bases).
+ * on != 0: a mate's length is the offset of the first zero byte of its row --
+ * the bases stand at the row's start (never 0: N is 'z'), every byte from the
+ * mate's end to the end of the row (cfg.read_stride bytes) is 0, and a row
+ * without a zero among its first cfg.read_len bytes holds cfg.read_len bases.
+ * cfg.read_len is then the longest mate; both strides work.  Every call that
+ * takes d_reads keeps its signature (smash_count_batch*, smash_phase_map,
+ * smash_phase_map_ahead, smash_phase_search_ahead, smash_count_fastq): each
+ * search first turns its batch's rows into lengths on its own stream, and the
+ * search, resolve, tags, smashMEM filters, key and positions use each mate's
+ * own length, as the reference does with trimmed reads.  A mate shorter than
+ * min_len (length 0 included) has no hits.  slots, smash_pipeline_max_batch
+ * and the key set do not change.  The searches go through read records (the
+ * direct-row search is for one length).  May be switched between runs (at a
+ * reset); SMASH_ERR_ARG while a look-ahead search is pending. */
+int smash_pipeline_var_len(smash_pipeline *p, int on);
 
 /* The positions the last batch emitted, in order: pos0 (0-based, smashMEM.py
  * column 5) and absolute position (pos0 + chrom_sizes.txt col 3) -- the
@@ -449,6 +467,10 @@ int smash_bin_positions(const int64_t *d_pos0, const int64_t *d_abspos,
  * (tid << 48 | pos0) in h_hits[q*2*slots ...]. slots = read_len - min_len + 1. */
 int smash_pipeline_peek(smash_pipeline *p, int32_t *h_nk, uint8_t *h_keep,
                         uint64_t *h_hits, uint64_t *h_hash);
+/* The same view of the last batch's 2 * n_pairs mate lengths (mate 2q = read
+ * 1 of pair q): what the device read from the rows in variable-length mode,
+ * cfg.read_len for each otherwise.  Synchronises. */
+int smash_pipeline_peek_lens(smash_pipeline *p, uint16_t *h_lens);
 
 /* ========================================================================== */
 /* mapout SAM writer: replaces Aligner::prepare_matches + print_matches       */
@@ -520,7 +542,17 @@ void smash_sam_free(char *text);
 /* pair; every mate must have it.  *n_pairs < max_pairs means the end.        */
 /* smash_strnum_order: perm[] = stable `samtools sort -n` order (strnum_cmp)  */
 /* of n NUL-padded names.  Host code only.                                    */
+/* Mixed read lengths: *len = SMASH_LEN_VAR | M on input (smash_fastq_read,   */
+/* smash_fastq_read_parallel, smash_fastq_index_open) packs mates of 1..M     */
+/* bases into rows of M bytes (M in 1..255), zero padded past each mate --    */
+/* the rows of a variable-length pipeline (smash_pipeline_var_len); a longer  */
+/* mate is SMASH_ERR_ARG naming the read; the empty-mate rules are the same.  */
+/* M = 0: the longest mate of the input (the parallel and the index reader;   */
+/* smash_fastq_read, which cannot know it, answers SMASH_ERR_ARG).  On return */
+/* *len = M without the flag.  smash_fastq_shard_open answers                 */
+/* SMASH_ERR_UNSUPPORTED to the flag (use smash_fastq_index).                 */
 /* ========================================================================== */
+#define SMASH_LEN_VAR 0x80000000u
 typedef struct smash_fastq smash_fastq;
 int smash_fastq_open(const char *const *r1_paths, uint32_t n1,
                      const char *const *r2_paths, uint32_t n2, smash_fastq **out);
@@ -536,7 +568,9 @@ int smash_strnum_order(const char *names, uint32_t stride, uint64_t n, uint64_t 
 /* feed its workers (query.cpp:614-740).  The two mate lists (gzip or plain)  */
 /* are parsed on two threads into pinned host batches of cfg.max_pairs pairs  */
 /* (`threads` workers convert / check them: replaceN + lowercase, pairs as    */
-/* smash_fastq_read, every mate of cfg.read_len bases), copied H2D on an own  */
+/* smash_fastq_read, every mate of cfg.read_len bases -- of 1..cfg.read_len   */
+/* bases on a variable-length pipeline, smash_pipeline_var_len, whose files   */
+/* are read with SMASH_LEN_VAR | cfg.read_len), copied H2D on an own          */
 /* stream into two device buffers, and counted with smash_count_batch on      */
 /* `stream`: parse, copy and compute of consecutive batches overlap.          */
 /*  sort_names = 0: the input is in samtools sort -n order already (checked   */

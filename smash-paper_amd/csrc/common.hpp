@@ -192,6 +192,9 @@ struct SearchWs {
   // the pipeline's packed-index searches: match words carry the map hint
   // (sm::Ctx::mhint; bits 40..47, the post stage masks the reference to 40)
   bool mhint = false;
+  // with d_lens: the longest read of the launch (1..255), which sizes the
+  // LDS row and the records; 0: unknown, rows for 255 bases
+  uint32_t geom_len = 0;
 };
 int map_batch_impl(const smash_index *ix, int mode, uint32_t min_len, const uint8_t *d_seqs,
                    uint64_t stride, const uint16_t *d_lens, uint32_t len, uint64_t n_reads,

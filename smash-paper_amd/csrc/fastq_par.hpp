@@ -410,6 +410,7 @@ struct Plan {
   uint64_t n_out = 0;
   std::vector<uint64_t> idx;
   uint32_t L = 0;
+  bool var = false;   // SMASH_LEN_VAR: mates of 1..L bases, rows of L bytes zero padded
 };
 
 // Plan the emission of all indexed pairs (fastqs_to_sam.cpp:80 + the
@@ -420,12 +421,40 @@ struct Plan {
 //  * order: check_order -- every kept pair's read-1 name >= the previous
 //    kept pair's under strnum_cmp, else error; sort -- kept pairs stably
 //    ordered by read-1 name.
+// L = SMASH_LEN_VAR | M: mates of mixed lengths, 1..M bases each (M = 0: the
+// longest mate of the input, <= 255); a longer mate is the error then.
 // All of it on T threads, before any pair is emitted.  Returns SMASH_OK or
 // an error code with msg.
 inline int plan_pairs(const PairIndex &px, uint32_t T, uint32_t L, bool check_order, bool sort,
                       Plan &pl, std::string &msg) {
   const uint64_t n = px.n;
   pl = Plan();
+  const bool var = (L & SMASH_LEN_VAR) != 0;
+  L &= ~SMASH_LEN_VAR;
+  pl.var = var;
+  if (var && L > 255) {
+    msg = "the maximum read length must be 1..255";
+    return SMASH_ERR_ARG;
+  }
+  if (var && !L) {   // the longest mate
+    const uint32_t R = std::max<uint32_t>(1, std::min<uint64_t>(T * 4, (n + 4095) / 4096));
+    std::vector<uint32_t> mx(R, 0);
+    std::atomic<uint32_t> next{0};
+    run_threads(std::min(T, R), [&](uint32_t) {
+      for (uint32_t r; (r = next++) < R;) {
+        uint32_t m = 0;
+        for (uint64_t i = n * r / R, hi = n * (r + 1) / R; i < hi; ++i)
+          m = std::max({m, parse(px.r1[i]).sn, parse(px.r2[i]).sn});
+        mx[r] = m;
+      }
+    });
+    L = *std::max_element(mx.begin(), mx.end());
+    if (L > 255) {
+      msg = "reads longer than 255 bases";
+      return SMASH_ERR_UNSUPPORTED;
+    }
+    if (!L) L = 1;   // (no pair kept: any width)
+  }
   const bool given = L != 0;   // (the messages of the streaming readers)
   if (!L) {   // the first kept pair's length
     for (uint64_t i = 0; i < n; ++i) {
@@ -463,7 +492,7 @@ inline int plan_pairs(const PairIndex &px, uint32_t T, uint32_t L, bool check_or
           continue;
         }
         if (a.sn == 0 || b.sn == 0) e = 1;
-        else if (a.sn != L || b.sn != L) e = 2;
+        else if (var ? (a.sn > L || b.sn > L) : (a.sn != L || b.sn != L)) e = 2;
         if (e && fb == ~0ull) {
           fb = i;
           kd = e;
@@ -490,6 +519,8 @@ inline int plan_pairs(const PairIndex &px, uint32_t T, uint32_t L, bool check_or
   for (uint32_t r = 0; r < R; ++r)
     if (first_bad[r] != ~0ull) {
       msg = kind[r] == 1 ? "one mate of a pair has no bases (" + name_of(first_bad[r]) + ")"
+            : var   ? "a mate is longer than the maximum read length, " + std::to_string(L) +
+                          " (" + name_of(first_bad[r]) + ")"
             : given ? "every mate must have the pipeline's read length, " + std::to_string(L) +
                           " (" + name_of(first_bad[r]) + ")"
                     : "all mates must have the same length (" + name_of(first_bad[r]) + ")";
@@ -605,8 +636,15 @@ inline bool pack_pairs(const PairIndex &px, const Plan &pl, uint64_t k0, uint64_
         const uint64_t i = pl.idx.empty() ? k : pl.idx[k];
         const Rec a = parse(px.r1[i]), b = parse(px.r2[i]);
         uint8_t *d = out + (k - k0) * 2 * RW;
-        convert(d, a.seq, L);
-        convert(d + RW, b.seq, L);
+        if (pl.var) {   // (checked by plan_pairs: sn <= L)
+          convert(d, a.seq, a.sn);
+          memset(d + a.sn, 0, L - a.sn);
+          convert(d + RW, b.seq, b.sn);
+          memset(d + RW + b.sn, 0, L - b.sn);
+        } else {
+          convert(d, a.seq, L);
+          convert(d + RW, b.seq, L);
+        }
         if (names) {
           if (a.nn >= stride) {
             bad = 1;

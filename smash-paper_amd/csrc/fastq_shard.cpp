@@ -875,6 +875,10 @@ extern "C" int smash_fastq_shard_open(const char *const *r1, uint32_t n1, const 
     set_error("smash_fastq_shard_open: bad arguments");
     return SMASH_ERR_ARG;
   }
+  if (*len & SMASH_LEN_VAR) {   // (dist.open_fastq falls back to smash_fastq_index)
+    set_error("smash_fastq_shard_open: mixed read lengths (SMASH_LEN_VAR) need smash_fastq_index");
+    return SMASH_ERR_UNSUPPORTED;
+  }
   auto h = std::make_unique<smash_fastq_shards>();
   h->threads = threads ? threads : 1;
   std::string msg;

@@ -37,6 +37,7 @@ using smash::ingest::strnum_cmp;
 namespace smash {
 uint32_t pipe_read_len(const smash_pipeline *p);
 uint32_t pipe_stride(const smash_pipeline *p);
+bool pipe_var_len(const smash_pipeline *p);
 uint64_t pipe_max_pairs(const smash_pipeline *p);
 int pipe_device(const smash_pipeline *p);
 void *&pipe_feed(smash_pipeline *p, void (*freer)(void *));
@@ -110,6 +111,9 @@ struct Feed {
   smash_pipeline *p;
   uint32_t L, T;
   uint32_t S;   // bytes per mate row in the batches (the pipeline's read stride)
+  // a variable-length pipeline: mates of 1..L bases, each row zero from its
+  // mate's end to L (the slots are reused: a row's last mate may have been longer)
+  bool var = false;
   uint64_t B;
   Reader r1, r2;
   Chunk c1, c2;
@@ -125,6 +129,21 @@ struct Feed {
   double ingest_s = 0;
   double index_s = 0;      // parallel path: map / inflate + index + checks, before batch 0
   bool parallel = false;   // the parallel producer ran
+
+  // a mate's length is wrong for this pipeline
+  bool bad_len(uint64_t la, uint64_t lb) const {
+    return var ? (la > L || lb > L) : (la != L || lb != L);
+  }
+  std::string len_msg(const std::string &na) const {
+    return var ? "smash_count_fastq: a mate is longer than the pipeline's maximum read length, " +
+                     std::to_string(L) + " (" + na + ")"
+               : "smash_count_fastq: every mate must have the pipeline's read length (" + na + ")";
+  }
+  // one prepared mate of n bases (n = L unless var) into its row
+  void put_mate(uint8_t *d, const uint8_t *a, uint32_t n, const uint8_t *lut) const {
+    for (uint32_t j = 0; j < n; ++j) d[j] = lut[a[j]];
+    if (n < L) memset(d + n, 0, L - n);
+  }
 
   void fail(int e, const std::string &m) {
     std::lock_guard<std::mutex> g(mu);
@@ -166,7 +185,7 @@ struct Feed {
         int e = 0;
         if (la == 0 && lb == 0) keep[i] = 0;
         else if (la == 0 || lb == 0) e = 1;
-        else if (la != L || lb != L) e = 2;
+        else if (bad_len(la, lb)) e = 2;
         if (e) {
           uint64_t w = where.load();
           while (i < w && !where.compare_exchange_weak(w, i)) {
@@ -182,8 +201,7 @@ struct Feed {
     if (la == 0 || lb == 0)
       fail(SMASH_ERR_ARG, "smash_count_fastq: one mate of a pair has no bases (" + na + ")");
     else
-      fail(SMASH_ERR_ARG, "smash_count_fastq: every mate must have the pipeline's read length (" +
-                              na + ")");
+      fail(SMASH_ERR_ARG, len_msg(na));
     return false;
   }
 
@@ -238,8 +256,8 @@ struct Feed {
           const uint8_t *a = reinterpret_cast<const uint8_t *>(c1.bases.data() + c1.boff[i]);
           const uint8_t *bb = reinterpret_cast<const uint8_t *>(c2.bases.data() + c2.boff[i]);
           uint8_t *d = s.h + dst[i] * 2 * S;
-          for (uint32_t j = 0; j < L; ++j) d[j] = lut[a[j]];
-          for (uint32_t j = 0; j < L; ++j) d[S + j] = lut[bb[j]];
+          put_mate(d, a, uint32_t(c1.boff[i + 1] - c1.boff[i]), lut);
+          put_mate(d + S, bb, uint32_t(c2.boff[i + 1] - c2.boff[i]), lut);
         }
       });
       if (disorder.load() != ~0ull) {
@@ -281,7 +299,7 @@ struct Feed {
     int rc = px.build(r1.paths, r2.paths, T, m);
     if (rc == SMASH_ERR_UNSUPPORTED) return false;
     I::Plan pl;
-    if (rc == SMASH_OK) rc = I::plan_pairs(px, T, L, !sort_names, sort_names, pl, m);
+    if (rc == SMASH_OK) rc = I::plan_pairs(px, T, var ? (SMASH_LEN_VAR | L) : L, !sort_names, sort_names, pl, m);
     if (rc != SMASH_OK) {
       fail(rc, "smash_count_fastq: " + m);
       return true;
@@ -519,7 +537,7 @@ struct Feed {
           for (uint64_t i = lo; i < hi; ++i) {
             const I::Rec x = I::parse(pa[i]), y = I::parse(pb[i]);
             keep[i] = !(x.sn == 0 && y.sn == 0);
-            if (keep[i] && (x.sn == 0 || y.sn == 0 || x.sn != L || y.sn != L)) {
+            if (keep[i] && (x.sn == 0 || y.sn == 0 || bad_len(x.sn, y.sn))) {
               uint64_t w = where.load();
               while (i < w && !where.compare_exchange_weak(w, i)) {
               }
@@ -532,8 +550,7 @@ struct Feed {
           const std::string na(x.name, x.nn);
           fail(SMASH_ERR_ARG, (x.sn == 0 || y.sn == 0)
                                   ? "smash_count_fastq: one mate of a pair has no bases (" + na + ")"
-                                  : "smash_count_fastq: every mate must have the pipeline's read "
-                                    "length (" + na + ")");
+                                  : len_msg(na));
           shutdown();
           return true;
         }
@@ -567,8 +584,12 @@ struct Feed {
             prev = x.name;
             pn = x.nn;
             uint8_t *d = s.h + (k + dst[i]) * 2 * S;
-            I::convert(d, x.seq, L);
-            I::convert(d + S, y.seq, L);
+            I::convert(d, x.seq, var ? x.sn : L);
+            I::convert(d + S, y.seq, var ? y.sn : L);
+            if (var) {
+              memset(d + x.sn, 0, L - x.sn);
+              memset(d + S + y.sn, 0, L - y.sn);
+            }
           }
         });
         if (disorder.load() != ~0ull) {
@@ -658,8 +679,8 @@ struct Feed {
         reads.resize(o + 2 * L);
         const uint8_t *a = reinterpret_cast<const uint8_t *>(c1.bases.data() + c1.boff[i]);
         const uint8_t *bb = reinterpret_cast<const uint8_t *>(c2.bases.data() + c2.boff[i]);
-        for (uint32_t j = 0; j < L; ++j) reads[o + j] = lut[a[j]];
-        for (uint32_t j = 0; j < L; ++j) reads[o + L + j] = lut[bb[j]];
+        put_mate(reads.data() + o, a, uint32_t(c1.boff[i + 1] - c1.boff[i]), lut);
+        put_mate(reads.data() + o + L, bb, uint32_t(c2.boff[i + 1] - c2.boff[i]), lut);
         names.insert(names.end(), c1.names.data() + c1.noff[i], c1.names.data() + c1.noff[i + 1]);
         noff.push_back(names.size());
       }
@@ -721,6 +742,7 @@ extern "C" int smash_count_fastq(smash_pipeline *p, const char *const *r1, uint3
   f->p = p;
   f->L = smash::pipe_read_len(p);
   f->S = smash::pipe_stride(p);
+  f->var = smash::pipe_var_len(p);
   f->B = smash::pipe_max_pairs(p);
   // SMASH_FEED_BATCH: pairs per file-fed batch below the pipeline's
   // max_pairs (the device buffers are 2 x 2 B x stride bytes)

@@ -60,6 +60,17 @@ extern "C" int smash_fastq_read(smash_fastq *f, uint64_t max_pairs, uint32_t *le
     return SMASH_ERR_ARG;
   }
   *n_pairs = 0;
+  // SMASH_LEN_VAR | M: mates of 1..M bases in rows of M bytes, zero padded
+  const bool var = (*len & SMASH_LEN_VAR) != 0;
+  if (var) {
+    const uint32_t M = *len & ~SMASH_LEN_VAR;
+    if (M == 0 || M > 255) {
+      set_error("smash_fastq_read: SMASH_LEN_VAR needs the maximum read length, 1..255 (a "
+                "stream's longest mate is not known in advance)");
+      return SMASH_ERR_ARG;
+    }
+    f->L = *len = M;
+  }
   uint64_t q = 0;
   Chunk &c1 = f->c1, &c2 = f->c2;
   const uint8_t *lut = smash::ingest::lut();
@@ -94,14 +105,23 @@ extern "C" int smash_fastq_read(smash_fastq *f, uint64_t max_pairs, uint32_t *le
         }
         f->L = *len = uint32_t(la);
       }
-      if (la != *len || lb != *len) {
+      if (var && (la > *len || lb > *len)) {
+        set_error("smash_fastq_read: a mate is longer than the maximum read length, " +
+                  std::to_string(*len) + " (" + na + ")");
+        return SMASH_ERR_ARG;
+      }
+      if (!var && (la != *len || lb != *len)) {
         set_error("smash_fastq_read: all mates must have the same length (" + na + ")");
         return SMASH_ERR_ARG;
       }
       const char *a = c1.bases.data() + c1.boff[i], *b = c2.bases.data() + c2.boff[i];
       uint8_t *d = h_reads + q * 2 * *len;
-      for (uint32_t j = 0; j < *len; ++j) d[j] = lut[uint8_t(a[j])];
-      for (uint32_t j = 0; j < *len; ++j) d[*len + j] = lut[uint8_t(b[j])];
+      for (uint32_t j = 0; j < la; ++j) d[j] = lut[uint8_t(a[j])];
+      for (uint32_t j = 0; j < lb; ++j) d[*len + j] = lut[uint8_t(b[j])];
+      if (var) {
+        memset(d + la, 0, *len - la);
+        memset(d + *len + lb, 0, *len - lb);
+      }
       if (h_names) {
         if (na.size() >= name_stride) {
           set_error("smash_fastq_read: read name longer than name_stride - 1: " + na);

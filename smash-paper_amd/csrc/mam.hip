@@ -106,6 +106,13 @@ int run_sm(const smash_index *ix, const sm::Ctx<IdxT> &c0, uint64_t n_reads, siz
     const int cap = std::atoi(e);
     if (cap >= 1 && cap < per_cu) per_cu = cap;
   }
+  // SMASH_SM_OCC=1: the launch's residency on stderr (tools/varlen_probe.py):
+  // blocks of one wave each per CU, over the CU's 4 SIMDs
+  if (const char *e = std::getenv("SMASH_SM_OCC"))
+    if (e[0] == '1')
+      std::fprintf(stderr, "[k_mam_sm] occupancy: %d blocks/CU = %.2f waves/SIMD, LDS row %u words "
+                           "(%zu B/block), lens %d, direct %u\n",
+                   per_cu, per_cu * (B / 64) / 4.0, c0.w_row, lds, c0.lens ? 1 : 0, c0.direct);
   uint64_t blocks = uint64_t(per_cu) * uint64_t(cus);
   const uint64_t want = (n_reads + B - 1) / B;
   if (blocks > want) blocks = want;
@@ -183,7 +190,9 @@ int launch_sm(const smash_index *ix, uint32_t min_len, const uint8_t *seqs,
               uint64_t n_reads, uint64_t *out, uint32_t cap, uint32_t *n_out,
               hipStream_t s, bool sync_check, const SearchWs *ws) {
   constexpr int B = kSmBlock;
-  const sm::Geom g = sm::make_geom(lens ? 255 : len);
+  // (per-read lengths: rows for the longest read the caller names, else 255)
+  const uint32_t glen = !lens ? len : ws && ws->geom_len ? ws->geom_len : 255u;
+  const sm::Geom g = sm::make_geom(glen);
   // direct rows: the reads are the device's native rows (16-byte aligned,
   // 4 w_row bytes apart, zero padded: smash_read_stride) -- the search DMAs
   // each straight from its row and needs no records
@@ -205,7 +214,7 @@ int launch_sm(const smash_index *ix, uint32_t min_len, const uint8_t *seqs,
     ix->rec_bytes = bytes;
   }
   if (!ws) rec = ix->d_rec;
-  const uint32_t ga = sm::prep_groups(lens ? 255 : len);
+  const uint32_t ga = sm::prep_groups(glen);
   // records (not for direct rows): k_prep (LDS-staged, the default:
   // profiles/r03/sched) or, with SMASH_PREP_LDS=0, k_prep_direct (no LDS: it
   // fits beside a running search but moves ~2x the bytes)

@@ -80,6 +80,13 @@ struct smash_pipeline {
   uint8_t *d_rec_s[2] = {nullptr, nullptr};
   unsigned long long *d_work_s[2] = {nullptr, nullptr};
   uint64_t rec_bytes = 0;
+  // variable-length mode (smash_pipeline_var_len): a mate's length is the
+  // offset of the first zero byte of its row (read_len: none); k_row_lens
+  // writes set k's lengths ahead of its search, and the post stage of the
+  // batch searched into set k reads them (allocated by the first such search)
+  bool var_len = false;
+  uint16_t *d_len_s[2] = {nullptr, nullptr};
+  const uint16_t *d_lens = nullptr;   // the current set's, null in fixed-length mode
   hipStream_t xs[2] = {nullptr, nullptr};
   hipEvent_t ev_in = nullptr, ev_found[2] = {nullptr, nullptr}, ev_free[2] = {nullptr, nullptr};
   hipEvent_t ev_done = nullptr;   // recorded once at creation: "inputs already complete"
@@ -204,6 +211,9 @@ struct PostCfg {
   // the search's map hints (SearchWs::mhint): a forward match word carries
   // its right map.bin byte before the edge rule in bits 40..47 (0: none)
   bool mhint;
+  // variable-length kernels (VAR): the batch's 2 * n_pairs mate lengths
+  // (k_row_lens); L above is then the longest a mate can be
+  const uint16_t *lens;
 };
 
 // the reference position of a match word: 48 bits (smash_gpu.h), 40 when
@@ -252,10 +262,12 @@ __device__ inline unsigned mapb(const PostCfg &c, uint64_t at) {
 }
 
 // resolve + merge + to_print order + tags for one mate; returns #hits
+// (VAR: the mate has Lm bases, its matches come from a search of Lm bases)
+template <bool VAR>
 __device__ int mate_hits(const PostCfg &c, const uint64_t *m, uint32_t n,
-                         Hit *hits, Aln *a, int32_t &err) {
+                         Hit *hits, Aln *a, int32_t &err, uint32_t Lm) {
   int na = 0;
-  const uint32_t L = c.L;
+  const uint32_t L = VAR ? Lm : c.L;
   for (uint32_t k = 0; k < n; ++k) {
     const uint64_t w = m[k];
     const uint64_t ref = w & (c.mhint ? kRefMask : 0xFFFFFFFFFFFFull);
@@ -353,6 +365,7 @@ __host__ __device__ inline uint64_t post_ws_bytes(uint32_t slots) {
   return (uint64_t(slots) * sizeof(Aln) + 2ull * slots * sizeof(Hit) + 15) & ~uint64_t(15);
 }
 
+template <bool VAR>
 __device__ __noinline__ void post_pair(const PostCfg &c, const uint64_t *__restrict__ match,
                                        const uint32_t *__restrict__ nmatch, uint64_t q,
                                        int32_t *nk_out, uint32_t *nmajor_out,
@@ -364,8 +377,11 @@ __device__ __noinline__ void post_pair(const PostCfg &c, const uint64_t *__restr
     Hit *h2 = h1 + c.slots;
     const uint32_t n1 = nmatch[2 * q], n2 = nmatch[2 * q + 1];
     nm = n1 + n2;
-    const int k1 = mate_hits(c, match + (2 * q) * c.slots, n1 < c.slots ? n1 : c.slots, h1, a, err);
-    const int k2 = mate_hits(c, match + (2 * q + 1) * c.slots, n2 < c.slots ? n2 : c.slots, h2, a, err);
+    const uint32_t L1 = VAR ? c.lens[2 * q] : 0u, L2 = VAR ? c.lens[2 * q + 1] : 0u;
+    const int k1 = mate_hits<VAR>(c, match + (2 * q) * c.slots, n1 < c.slots ? n1 : c.slots, h1, a,
+                                  err, L1);
+    const int k2 = mate_hits<VAR>(c, match + (2 * q + 1) * c.slots, n2 < c.slots ? n2 : c.slots, h2,
+                                  a, err, L2);
     if (n1 > c.slots || n2 > c.slots) err = SMASH_ERR_UNSUPPORTED;
     // smashMEM excess-mappability filter (smashMEM.py:84-92)
     int m1 = 0, m2 = 0;
@@ -448,6 +464,8 @@ __device__ __forceinline__ void post_stats(unsigned long long nm, unsigned long 
 
 // general path: every pair (list == nullptr), or the pairs listed by
 // k_post_fast; grid-stride, kPostThreads threads, one workspace slice each
+// (VAR: every mate's own length, PostCfg::lens, instead of c.L)
+template <bool VAR>
 __global__ __launch_bounds__(kB) void k_post(PostCfg c, const uint64_t *__restrict__ match,
                                              const uint32_t *__restrict__ nmatch,
                                              uint64_t n_pairs, const uint32_t *list,
@@ -463,12 +481,59 @@ __global__ __launch_bounds__(kB) void k_post(PostCfg c, const uint64_t *__restri
   const uint64_t n = list ? *n_list : n_pairs;
   for (uint64_t i = t; i < n; i += uint64_t(gridDim.x) * blockDim.x) {
     unsigned long long m = 0;
-    post_pair(c, match, nmatch, list ? list[i] : i, nk_out, nmajor_out, hits_out, hash_out, err,
+    post_pair<VAR>(c, match, nmatch, list ? list[i] : i, nk_out, nmajor_out, hits_out, hash_out, err,
               m, my);
     nm += m;
     ++np;
   }
   post_stats(nm, np, err, stats);
+}
+
+// the offset of the first zero byte of w (4: none)
+__device__ __forceinline__ uint32_t zero_byte(uint32_t w) {
+  const uint32_t z = (w - 0x01010101u) & ~w & 0x80808080u;   // lowest flag: a true zero byte
+  return z ? uint32_t(__builtin_ctz(z)) >> 3 : 4u;
+}
+
+// Variable-length mode: lens[r] = the offset of the first zero byte among
+// the first max_len bytes of row r, max_len when there is none (bases are
+// never 0: the rows are zero padded past the mate).  One thread per mate.
+// Native rows (wide: the base 16-byte aligned, the stride a multiple of 16
+// and at least max_len rounded up to 16) take 16-byte loads; any other row
+// its aligned words, and single bytes before the first and after the last
+// whole one.  Every load lies inside [row, row + max_len rounded up to 16)
+// (wide) or [row, row + max_len) (else), so none passes n * stride.
+__global__ __launch_bounds__(kB) void k_row_lens(const uint8_t *__restrict__ rows, uint64_t stride,
+                                                 uint32_t max_len, uint64_t n, bool wide,
+                                                 uint16_t *__restrict__ lens) {
+  SMASH_BESIDE_SEARCH();
+  const uint64_t r = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (r >= n) return;
+  const uint8_t *row = rows + r * stride;
+  uint32_t i = 0;
+  bool found = false;
+  if (wide) {
+    const uint4 *v = reinterpret_cast<const uint4 *>(row);
+    for (uint32_t c = 0; c < max_len && !found; c += 16) {
+      const uint4 x = v[c >> 4];
+      const uint32_t w[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+      for (int k = 3; k >= 0; --k) {   // (the lowest word with a zero byte wins)
+        const uint32_t z = zero_byte(w[k]);
+        if (z < 4) { found = true; i = c + 4 * uint32_t(k) + z; }
+      }
+    }
+  } else {
+    for (; i < max_len && ((reinterpret_cast<uintptr_t>(row) + i) & 3); ++i)
+      if (row[i] == 0) { found = true; break; }
+    for (; !found && i + 4 <= max_len; i += 4) {
+      const uint32_t z = zero_byte(*reinterpret_cast<const uint32_t *>(row + i));
+      if (z < 4) { found = true; i += z; break; }
+    }
+    for (; !found && i < max_len; ++i)
+      if (row[i] == 0) { found = true; break; }
+  }
+  lens[r] = uint16_t(found && i < max_len ? i : max_len);
 }
 
 // ---------------------------------------------------------------------------
@@ -546,11 +611,11 @@ __device__ __forceinline__ void sort_net(uint64_t (&v)[N]) {
 // hint already gave) reads a fixed address instead (c.map: one hot line), so
 // no load waits on a branch and the rounds overlap their slots' latencies
 // (each slot was a chain of ~4 dependent loads, one slot after the other).
+// (L: the mate's length, c.L in the fixed-length kernels)
 template <int CAP>
 __device__ __forceinline__ void mate_fast(const PostCfg &c, const uint64_t *__restrict__ sp,
                                           const uint64_t *m, uint32_t n, uint64_t (&H)[CAP],
-                                          int32_t &err) {
-  const uint32_t L = c.L;
+                                          int32_t &err, const uint32_t L) {
   uint64_t A[CAP];
   uint32_t R[CAP];   // payload through the sort: left byte | right byte << 8 | small << 16
   uint64_t w[CAP];
@@ -679,7 +744,8 @@ __device__ __forceinline__ bool hit_kept(uint64_t h) { return h != ~0ull && ((h 
 // CAP words per mate (8: the common case; a pair with a mate above `lim`
 // goes to the `up` list, for k_post_fast<16> or, past 16, k_post).  Pairs:
 // all n_pairs (list == nullptr) or the *n_list listed ones (grid-stride).
-template <int CAP>
+// VAR: every mate's own length (PostCfg::lens) instead of c.L.
+template <int CAP, bool VAR>
 __global__ __launch_bounds__(kB) void k_post_fast(PostCfg c, const uint64_t *__restrict__ match,
                                                   const uint32_t *__restrict__ nmatch,
                                                   uint64_t n_pairs, const uint32_t *list,
@@ -707,8 +773,9 @@ __global__ __launch_bounds__(kB) void k_post_fast(PostCfg c, const uint64_t *__r
       nm += n1 + n2;
       ++np;
       uint64_t H1[CAP], H2[CAP];
-      mate_fast<CAP>(c, sp, match + (2 * q) * c.slots, n1, H1, err);
-      mate_fast<CAP>(c, sp, match + (2 * q + 1) * c.slots, n2, H2, err);
+      mate_fast<CAP>(c, sp, match + (2 * q) * c.slots, n1, H1, err, VAR ? c.lens[2 * q] : c.L);
+      mate_fast<CAP>(c, sp, match + (2 * q + 1) * c.slots, n2, H2, err,
+                     VAR ? c.lens[2 * q + 1] : c.L);
       // (8 words per mate: at most 16 kept hits, the head row; 16 per mate:
       // the full row, copied to the head row below when they fit)
       uint64_t *ho = CAP <= 8 ? hits_out.head + q * kHitHead
@@ -1256,6 +1323,7 @@ PostCfg post_cfg(const smash_pipeline *p) {
   c.sp_shift = p->sp_shift;
   c.sp_ncell = p->sp_ncell;
   c.mhint = p->mhint;
+  c.lens = p->d_lens;
   return c;
 }
 
@@ -1517,6 +1585,7 @@ extern "C" int smash_pipeline_create(const smash_index *ix,
 namespace smash {
 uint32_t pipe_read_len(const smash_pipeline *p) { return p->read_len; }
 uint32_t pipe_stride(const smash_pipeline *p) { return p->stride; }
+bool pipe_var_len(const smash_pipeline *p) { return p->var_len; }
 uint64_t pipe_max_pairs(const smash_pipeline *p) { return p->max_pairs; }
 int pipe_device(const smash_pipeline *p) { return p->device; }
 void *&pipe_feed(smash_pipeline *p, void (*freer)(void *)) {
@@ -1538,7 +1607,7 @@ extern "C" void smash_pipeline_free(smash_pipeline *p) {
     if (p->ev_found[k]) (void)hipEventDestroy(p->ev_found[k]);
     if (p->ev_free[k]) (void)hipEventDestroy(p->ev_free[k]);
     for (void *q : {(void *)p->d_match_s[k], (void *)p->d_nmatch_s[k], (void *)p->d_rec_s[k],
-                    (void *)p->d_work_s[k]})
+                    (void *)p->d_work_s[k], (void *)p->d_len_s[k]})
       dfree(q);
   }
   if (p->ev_in) (void)hipEventDestroy(p->ev_in);
@@ -1585,15 +1654,32 @@ static int search_into(smash_pipeline *p, int k, const uint8_t *d_reads, uint64_
     p->ix->kev[0] = p->ev[2 * p->n_ev];          // recorded around k_mam_sm itself
     p->ix->kev[1] = p->ev[2 * p->n_ev + 1];
   }
-  if (!search_direct(d_reads, p->stride, p->read_len) && !p->d_rec_s[k]) {   // k_prep's records
-    SMASH_HIP(hipStreamSynchronize(xs));
+  // (variable lengths: always through records, which carry each mate's own bad mask)
+  if ((p->var_len || !search_direct(d_reads, p->stride, p->read_len)) && !p->d_rec_s[k]) {
+    SMASH_HIP(hipStreamSynchronize(xs));   // k_prep's records
     SMASH_HIP(hipMalloc(reinterpret_cast<void **>(&p->d_rec_s[k]), p->rec_bytes));
   }
-  const SearchWs ws{p->d_rec_s[k], p->d_rec_s[k] ? p->rec_bytes : 0, p->d_work_s[k],
-                    p->set_used[k] && !p->gate_prep ? p->ev_free[k] : nullptr, p->mhint};
-  const int rc = map_batch_impl(p->ix, SMASH_MODE_MAM, p->min_len, d_reads, p->stride, nullptr,
-                                p->read_len, 2 * n_pairs, p->d_match_s[k], p->slots,
-                                p->d_nmatch_s[k], xs, false, &ws);   // probe check at stats time
+  if (p->var_len) {
+    if (!p->d_len_s[k]) {
+      SMASH_HIP(hipStreamSynchronize(xs));
+      SMASH_HIP(hipMalloc(reinterpret_cast<void **>(&p->d_len_s[k]), 2 * 2 * p->max_pairs));
+    }
+    // the set's lengths were last read by its previous batch's post stage
+    // (the records' gate below comes after k_prep: this one before k_row_lens)
+    if (p->set_used[k] && !p->gate_prep) SMASH_HIP(hipStreamWaitEvent(xs, p->ev_free[k], 0));
+    const bool wide = (reinterpret_cast<uintptr_t>(d_reads) & 15) == 0 && p->stride % 16 == 0 &&
+                      p->stride >= ((p->read_len + 15u) & ~15u);
+    k_row_lens<<<grid_for(2 * n_pairs, kB, 1u << 30), kB, 0, xs>>>(
+        d_reads, p->stride, p->read_len, 2 * n_pairs, wide, p->d_len_s[k]);
+    SMASH_HIP(hipGetLastError());
+  }
+  SearchWs ws{p->d_rec_s[k], p->d_rec_s[k] ? p->rec_bytes : 0, p->d_work_s[k],
+              p->set_used[k] && !p->gate_prep ? p->ev_free[k] : nullptr, p->mhint};
+  ws.geom_len = p->read_len;
+  const int rc = map_batch_impl(p->ix, SMASH_MODE_MAM, p->min_len, d_reads, p->stride,
+                                p->var_len ? p->d_len_s[k] : nullptr, p->read_len, 2 * n_pairs,
+                                p->d_match_s[k], p->slots, p->d_nmatch_s[k], xs, false,
+                                &ws);   // probe check at stats time
   p->ix->kev[0] = p->ix->kev[1] = nullptr;
   if (rc) return rc;
   if (p->prof) {
@@ -1605,6 +1691,36 @@ static int search_into(smash_pipeline *p, int k, const uint8_t *d_reads, uint64_
   p->pref_reads[k] = d_reads;
   p->pref_n[k] = n_pairs;
   p->searched[k] = true;
+  return SMASH_OK;
+}
+
+// the post stage of the current set's batch on s (VAR: the variable-length
+// instantiations, which read the set's lengths)
+template <bool VAR>
+static int post_stage(smash_pipeline *p, uint64_t n_pairs, hipStream_t s) {
+  if (p->post_fast) {
+    // mates of <= 8 matches (most pairs) in 8-word networks, <= 16 in
+    // 16-word ones, the rest in the general kernel
+    SMASH_HIP(hipMemsetAsync(p->d_fb, 0, 4, s));
+    SMASH_HIP(hipMemsetAsync(p->d_l16, 0, 4, s));
+    const PostCfg pc = post_cfg(p);
+    k_post_fast<8, VAR><<<grid_for(n_pairs, kB, 1u << 30), kB, 0, s>>>(
+        pc, p->d_match, p->d_nmatch, n_pairs, nullptr, nullptr, std::min(8u, p->post_cap),
+        p->d_l16 + 1, p->d_l16, p->d_nk, p->d_nmajor, hit_rows(p), p->d_hash, p->d_stats);
+    SMASH_HIP(hipGetLastError());
+    k_post_fast<FCAP, VAR><<<grid_for(n_pairs, kB, 1024), kB, 0, s>>>(
+        pc, p->d_match, p->d_nmatch, n_pairs, p->d_l16 + 1, p->d_l16, p->post_cap,
+        p->d_fb + 1, p->d_fb, p->d_nk, p->d_nmajor, hit_rows(p), p->d_hash, p->d_stats);
+    SMASH_HIP(hipGetLastError());
+    k_post<VAR><<<kPostBlocks, kB, 0, s>>>(post_cfg(p), p->d_match, p->d_nmatch, n_pairs,
+                                           p->d_fb + 1, p->d_fb, p->d_nk, p->d_nmajor, hit_rows(p),
+                                           p->d_hash, p->d_stats, p->d_post_ws);
+  } else {
+    k_post<VAR><<<kPostBlocks, kB, 0, s>>>(post_cfg(p), p->d_match, p->d_nmatch, n_pairs, nullptr,
+                                           nullptr, p->d_nk, p->d_nmajor, hit_rows(p), p->d_hash,
+                                           p->d_stats, p->d_post_ws);
+  }
+  SMASH_HIP(hipGetLastError());
   return SMASH_OK;
 }
 
@@ -1637,34 +1753,15 @@ static int phase_map_impl(smash_pipeline *p, const uint8_t *d_reads, uint64_t n_
   }
   if (!have && (rc = search_into(p, k, d_reads, n_pairs, in_ev))) return rc;
   p->searched[k] = false;   // consumed by this batch
+  // (the set's lengths: allocated and written by its search, above or ahead)
+  p->d_lens = p->var_len ? p->d_len_s[k] : nullptr;
   const bool next_have = p->searched[k ^ 1] && p->pref_reads[k ^ 1] == d_next &&
                          p->pref_n[k ^ 1] == n_next;   // (smash_phase_search_ahead)
   if (d_next && n_next && !next_have && (rc = search_into(p, k ^ 1, d_next, n_next, in_ev)))
     return rc;
   SMASH_HIP(hipStreamWaitEvent(s, p->ev_found[k], 0));
-  if (p->post_fast) {
-    // mates of <= 8 matches (most pairs) in 8-word networks, <= 16 in
-    // 16-word ones, the rest in the general kernel
-    SMASH_HIP(hipMemsetAsync(p->d_fb, 0, 4, s));
-    SMASH_HIP(hipMemsetAsync(p->d_l16, 0, 4, s));
-    const PostCfg pc = post_cfg(p);
-    k_post_fast<8><<<grid_for(n_pairs, kB, 1u << 30), kB, 0, s>>>(
-        pc, p->d_match, p->d_nmatch, n_pairs, nullptr, nullptr, std::min(8u, p->post_cap),
-        p->d_l16 + 1, p->d_l16, p->d_nk, p->d_nmajor, hit_rows(p), p->d_hash, p->d_stats);
-    SMASH_HIP(hipGetLastError());
-    k_post_fast<FCAP><<<grid_for(n_pairs, kB, 1024), kB, 0, s>>>(
-        pc, p->d_match, p->d_nmatch, n_pairs, p->d_l16 + 1, p->d_l16, p->post_cap,
-        p->d_fb + 1, p->d_fb, p->d_nk, p->d_nmajor, hit_rows(p), p->d_hash, p->d_stats);
-    SMASH_HIP(hipGetLastError());
-    k_post<<<kPostBlocks, kB, 0, s>>>(post_cfg(p), p->d_match, p->d_nmatch, n_pairs,
-                                      p->d_fb + 1, p->d_fb, p->d_nk, p->d_nmajor, hit_rows(p),
-                                      p->d_hash, p->d_stats, p->d_post_ws);
-  } else {
-    k_post<<<kPostBlocks, kB, 0, s>>>(post_cfg(p), p->d_match, p->d_nmatch, n_pairs, nullptr,
-                                      nullptr, p->d_nk, p->d_nmajor, hit_rows(p), p->d_hash,
-                                      p->d_stats, p->d_post_ws);
-  }
-  SMASH_HIP(hipGetLastError());
+  if ((rc = p->d_lens ? post_stage<true>(p, n_pairs, s) : post_stage<false>(p, n_pairs, s)))
+    return rc;
   if (!p->defer_free)
     SMASH_HIP(hipEventRecord(p->ev_free[k], s));   // the set's matches are read
   p->set_used[k] = true;
@@ -2307,6 +2404,30 @@ extern "C" int smash_pipeline_reset_ex(smash_pipeline *p, uint32_t flags, void *
 
 extern "C" int smash_pipeline_reset(smash_pipeline *p, void *stream) {
   return smash_pipeline_reset_ex(p, 0, stream);
+}
+
+extern "C" int smash_pipeline_var_len(smash_pipeline *p, int on) {
+  if (!p) return SMASH_ERR_ARG;
+  if (p->searched[0] || p->searched[1]) {   // (its lengths, or their absence, are the old mode's)
+    set_error("smash_pipeline_var_len: a look-ahead search is pending");
+    return SMASH_ERR_ARG;
+  }
+  p->var_len = on != 0;
+  return SMASH_OK;
+}
+
+extern "C" int smash_pipeline_peek_lens(smash_pipeline *p, uint16_t *h_lens) {
+  if (!p || !h_lens) return SMASH_ERR_ARG;
+  SMASH_HIP(hipSetDevice(p->device));
+  SMASH_HIP(hipDeviceSynchronize());
+  const uint64_t n = p->n_pairs;
+  if (!n) return SMASH_OK;
+  if (!p->d_lens) {   // fixed-length batch: every mate has cfg.read_len bases
+    std::fill(h_lens, h_lens + 2 * n, uint16_t(p->read_len));
+    return SMASH_OK;
+  }
+  SMASH_HIP(hipMemcpy(h_lens, p->d_lens, 2 * 2 * n, hipMemcpyDeviceToHost));
+  return SMASH_OK;
 }
 
 extern "C" int smash_pipeline_reads_resident(smash_pipeline *p, int on) {

@@ -274,6 +274,12 @@ def open_fastq(sc, r1_paths, r2_paths, sort_names=False, threads=0, read_len=0):
     smashgpu.FastqIndex, which every rank builds over the whole input --
     the same decision on every rank, since every rank sees every scan."""
     import smashgpu as S
+    if read_len & S.SMASH_LEN_VAR:
+        # mixed read lengths (SMASH_LEN_VAR | M): the rank-local reader answers
+        # SMASH_ERR_UNSUPPORTED to them -- straight to the whole-input index,
+        # without the scan exchange
+        return S.FastqIndex(r1_paths, r2_paths, threads=threads, read_len=read_len,
+                            sort_names=sort_names)
     try:
         return S.FastqShards(r1_paths, r2_paths, sc.rank, sc.world, sc.comm.all_gather_bytes,
                              threads=threads, read_len=read_len, sort_names=sort_names)

@@ -13,6 +13,8 @@ subcommand below takes the same inputs and writes the same files:
   count ID "R1.gz.." "R2.gz.." BINDIR
                                 map + varbin fused on the device, no positions
                                 file: ID.varbin.txt and ID.stats.txt
+                                (map / count --max-read-len N: mates of mixed
+                                lengths up to N, e.g. trimmed reads)
   memsam [-nomap] [--tag] QUERY.sam
                                 `mummer -rcref -samin -samout [-nomap]`: the
                                 mapout SAM file; --tag adds mappability_tag's
@@ -160,15 +162,24 @@ def strnum_cmp(a: bytes, b: bytes) -> int:
 strnum_key = functools.cmp_to_key(strnum_cmp)
 
 
-def reads_matrix(pairs):
+def reads_matrix(pairs, max_len=0):
     """[2n, L] uint8 mates (read 1, read 2, ...) after replaceN + lowercasing
-    (fastqs_to_sam.cpp:74 with argc == 4, query.cpp:125-144)."""
+    (fastqs_to_sam.cpp:74 with argc == 4, query.cpp:125-144).  max_len
+    (--max-read-len): mates of mixed lengths up to max_len in zero-padded rows
+    of max_len bytes, as a variable-length pipeline reads them."""
     if not pairs:
-        return np.zeros((0, 0), np.uint8)
+        return np.zeros((0, max_len), np.uint8)
+    if max_len:
+        for name, a, b in pairs:
+            if len(a) > max_len or len(b) > max_len:
+                raise SystemExit("read %s is longer than --max-read-len %d"
+                                 % (name.decode(errors="replace"), max_len))
+        return S.prepare_reads([m for _, a, b in pairs for m in (a, b)], max_len)
     L = len(pairs[0][1])
     if any(len(a) != L or len(b) != L for _, a, b in pairs):
         raise SystemExit("all mates must have the same length (the device batches are "
-                         "fixed-length); split the input by read length")
+                         "fixed-length); pass --max-read-len N to count mates of mixed "
+                         "lengths up to N")
     raw = np.frombuffer(b"".join(a + b for _, a, b in pairs), np.uint8).reshape(-1, L)
     return S.prepare_reads(raw)
 
@@ -246,13 +257,14 @@ class _Run:
             self.bins_rows, self.starts = S.read_bins(bins_path)
         else:
             self.bins_rows, self.starts = [], np.zeros(1, np.int64)
+        self.max_len = _max_read_len(args)
         if args.sam:
             pairs = sam_pairs(args.sam)
             pairs.sort(key=lambda p: strnum_key(p[0]))
-            self.reads = reads_matrix(pairs)
+            self.reads = reads_matrix(pairs, self.max_len)
             self.n = len(pairs)
         else:   # native ingest (smash_fastq_read) + samtools sort -n order
-            names, reads = S.read_fastq_pairs(args.reads1.split(), args.reads2.split())
+            names, reads = _read_pairs(args.reads1.split(), args.reads2.split(), self.max_len)
             order = S.strnum_order(names)
             n = len(names)
             self.reads = reads.reshape(n, -1)[order].reshape(2 * n, -1) if n else reads
@@ -262,9 +274,9 @@ class _Run:
 
     def run(self, on_batch):
         torch = self.torch
-        L = self.reads.shape[1] if self.n else 150
+        L = self.max_len or (self.reads.shape[1] if self.n else 150)
         pipe = S.Pipeline(self.ix, self.cs, self.starts, L, self.batch,
-                          dedup_capacity=max(self.n, 1))
+                          dedup_capacity=max(self.n, 1), var_len=bool(self.max_len))
         counts = torch.zeros(len(self.starts), dtype=torch.int64, device=self.dev)
         pipe.reset()
         for b0 in range(0, self.n, self.batch):
@@ -276,6 +288,34 @@ class _Run:
         if st.error:
             raise SystemExit("%s: %s" % (_err_label(st.error), S.ERRORS.get(st.error, st.error)))
         return counts.cpu().numpy(), st
+
+
+def _max_read_len(args):
+    """--max-read-len N: 0 (off: every mate has one length) or the row width
+    for N in 1..255 (a pipeline's rows are at least its minimum match length,
+    20, wide: a smaller N counts as 20 -- such mates have no hits either way)"""
+    m = getattr(args, "max_read_len", 0) or 0
+    if m and not 1 <= m <= 255:
+        raise SystemExit("--max-read-len must be 1..255")
+    return max(m, 20) if m else 0
+
+
+def _name_option(e, max_len):
+    """a reader's mixed-length error without --max-read-len, told about the option"""
+    if not max_len and ("same length" in str(e) or "pipeline's read length" in str(e)):
+        x = S.SmashError(str(e) + "; pass --max-read-len N to count mates of mixed lengths "
+                         "up to N")
+        x.code = getattr(e, "code", None)
+        return x
+    return e
+
+
+def _read_pairs(r1, r2, max_len):
+    """the native reader (mixed lengths with --max-read-len)"""
+    try:
+        return S.read_fastq_pairs(r1, r2, read_len=(S.SMASH_LEN_VAR | max_len) if max_len else 0)
+    except S.SmashError as e:
+        raise _name_option(e, max_len) from None
 
 
 def cmd_map(args):
@@ -328,12 +368,19 @@ def _count_files(args, bins):
     cs = S.read_chrom_sizes(args.chrom_sizes or ref + ".bin/chrom_sizes.txt")
     rows, starts = S.read_bins(bins)
     r1, r2 = args.reads1.split(), args.reads2.split()
-    L = S.first_read_length(r1)
-    cap = args.dedup_capacity or fastq_pairs_bound(r1, r2, L, args.batch)
-    pipe = S.Pipeline(ix, cs, starts, L, args.batch, dedup_capacity=cap)
+    M = _max_read_len(args)
+    L = M or S.first_read_length(r1)
+    # (mixed lengths: the file sizes do not bound the pairs usefully; the set
+    # starts at one batch and the feed grows it, as for gzip input)
+    cap = args.dedup_capacity or (max(int(args.batch), 1) if M else
+                                  fastq_pairs_bound(r1, r2, L, args.batch))
+    pipe = S.Pipeline(ix, cs, starts, L, args.batch, dedup_capacity=cap, var_len=bool(M))
     counts = torch.zeros(len(starts), dtype=torch.int64, device=torch.device("cuda", args.device))
     pipe.reset()
-    pipe.count_fastq(r1, r2, counts, sort_names=not args.presorted)
+    try:
+        pipe.count_fastq(r1, r2, counts, sort_names=not args.presorted)
+    except S.SmashError as e:
+        raise _name_option(e, M) from None
     st = pipe.stats(raise_on_error=False)
     if st.error:
         raise SystemExit("%s: %s" % (_err_label(st.error), S.ERRORS.get(st.error, st.error)))
@@ -367,14 +414,19 @@ def _count_files_dist(args, bins, world):
     # the pipeline is made once the plan (pairs, read length) is known: a
     # placeholder counter carries the communicator for the scan exchange
     sc = ShardedCounter(_NoPipe(), rank, world, dev, count_group=cpu)
-    fq = open_fastq(sc, r1, r2, sort_names=not args.presorted)
+    M = _max_read_len(args)
+    try:
+        fq = open_fastq(sc, r1, r2, sort_names=not args.presorted,
+                        read_len=(S.SMASH_LEN_VAR | M) if M else 0)
+    except S.SmashError as e:
+        raise _name_option(e, M) from None
     # an owner keeps the keys it owns for the whole run: ~pairs / world to
     # start with; unless --dedup-capacity fixes it, ShardedCounter grows each
     # owner's set after the first batch's export to the run's pairs x that
     # owner's measured share (a skewed owner is sized, not overflowed), and a
     # set that still overflows stops every rank at the next batch
     cap = args.dedup_capacity or (fq.n // world + fq.n // (8 * world) + (1 << 20))
-    pipe = S.Pipeline(ix, cs, starts, fq.L, args.batch, dedup_capacity=cap)
+    pipe = S.Pipeline(ix, cs, starts, fq.L, args.batch, dedup_capacity=cap, var_len=bool(M))
     counts = torch.zeros(len(starts), dtype=torch.int64, device=dev)
     sc = ShardedCounter(pipe, rank, world, dev, count_group=cpu,
                         plan_pairs=0 if args.dedup_capacity else fq.n)
@@ -558,16 +610,29 @@ def cmd_memsam(args):
             if not batch:
                 break
             L = len(batch[0][1])
-            if any(len(r[1]) != L for r in batch) or L == 0 or L > 255:
+            lens = None
+            if any(len(r[1]) != L for r in batch):
+                # mixed lengths, as mummer takes them (query.cpp:614-687 keeps no
+                # fixed length): rows of 255 bytes and a length per read
+                lens = np.array([len(r[1]) for r in batch], np.uint16)
+                if int(lens.min()) == 0 or int(lens.max()) > 255:
+                    raise SystemExit("every read must have 1..255 bases (device batches)")
+                L = 255
+                reads = np.zeros((len(batch), L), np.uint8)
+                for i, r in enumerate(batch):
+                    reads[i, :lens[i]] = np.frombuffer(r[1], np.uint8)
+                reads = S._LOWER[reads]
+            elif L == 0 or L > 255:
                 raise SystemExit("all reads must have one length in 1..255 (device batches)")
-            # NewQuery::extend lowercases only (replaceN is fastqs_to_sam's, upstream)
-            reads = S._LOWER[np.frombuffer(b"".join(r[1] for r in batch),
-                                           np.uint8).reshape(-1, L)]
+            else:
+                # NewQuery::extend lowercases only (replaceN is fastqs_to_sam's, upstream)
+                reads = S._LOWER[np.frombuffer(b"".join(r[1] for r in batch),
+                                               np.uint8).reshape(-1, L)]
             d = torch.from_numpy(np.ascontiguousarray(reads)).to(dev)
             text, terr = S.sam_lines(ix, d, L, [r[0] for r in batch], [r[1] for r in batch],
                                      [r[2] for r in batch], [r[3] for r in batch],
                                      nomap=args.nomap, tag_offsets=offsets, small_chr=small,
-                                     min_len=args.l)
+                                     min_len=args.l, lens=lens)
             out.write(text)
             if terr:
                 raise SystemExit(S.ERRORS.get(terr, terr))
@@ -592,6 +657,9 @@ def main(argv=None):
         p.add_argument("--sam", default=None, help="unmapped SAM input instead (mummer -samin)")
         p.add_argument("--chrom-sizes", default=None)
         p.add_argument("--batch", type=int, default=2_000_000, help="pairs per device batch")
+        p.add_argument("--max-read-len", type=int, default=0, metavar="N",
+                       help="mates of mixed lengths, each at most N bases (1..255; e.g. "
+                            "adapter- or quality-trimmed reads); default: one length")
         if name == "count":
             p.add_argument("--presorted", action="store_true",
                            help="FASTQ pairs already in samtools sort -n order: stream them")

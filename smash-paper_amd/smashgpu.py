@@ -28,6 +28,7 @@ i32p = C.POINTER(C.c_int32)
 vp = C.c_void_p
 
 SMASH_MODE_MAM = 1
+SMASH_LEN_VAR = 0x80000000   # readers: *len = SMASH_LEN_VAR | M, mates of 1..M bases
 SMASH_MODE_MAM_PLAIN = 2
 SMASH_MODE_MUM = 3
 SMASH_MODE_MEM = 4
@@ -47,6 +48,7 @@ EXPORTS = [
     "smash_phase_map", "smash_phase_export", "smash_dedup_owner",
     "smash_phase_import", "smash_phase_positions", "smash_phase_bin",
     "smash_pipeline_stats", "smash_pipeline_reset", "smash_pipeline_reset_ex", "smash_pipeline_reads_resident", "smash_pipeline_peek",
+    "smash_pipeline_var_len", "smash_pipeline_peek_lens",
     "smash_pipeline_profile", "smash_pipeline_profile_read",
     "smash_pipeline_positions", "smash_bin_positions", "smash_mappability_scan",
     "smash_sam_records", "smash_sam_format", "smash_sam_free",
@@ -179,6 +181,8 @@ def lib():
     L.smash_pipeline_reset_ex.argtypes = [vp, C.c_uint32, vp]
     L.smash_pipeline_reads_resident.argtypes = [vp, C.c_int]
     L.smash_pipeline_peek.argtypes = [vp, i32p, u8p, u64p, u64p]
+    L.smash_pipeline_var_len.argtypes = [vp, C.c_int]
+    L.smash_pipeline_peek_lens.argtypes = [vp, C.POINTER(C.c_uint16)]
     L.smash_pipeline_profile.argtypes = [vp, C.c_int]
     L.smash_pipeline_profile_read.argtypes = [vp, C.POINTER(C.c_double), u64p, u64p]
     L.smash_pipeline_positions.argtypes = [vp, i64p, i64p, C.c_uint64, u64p]
@@ -315,9 +319,26 @@ def text_from_contigs(contigs):
             names)
 
 
-def prepare_reads(seqs) -> np.ndarray:
+def prepare_reads(seqs, max_len=None) -> np.ndarray:
     """fastqs_to_sam replaceN (N->Z, fastqs_to_sam.cpp:289) + NewQuery::extend
-    lowercasing (query.cpp:125-144).  seqs: uint8 [n, L] ASCII."""
+    lowercasing (query.cpp:125-144).  seqs: uint8 [n, L] ASCII, or -- with
+    max_len -- a list of byte strings of mixed lengths (each at most max_len):
+    rows of max_len bytes, zero padded past each mate, as a variable-length
+    Pipeline (var_len=True) reads them."""
+    if max_len is not None:
+        if not 1 <= max_len <= 255:
+            raise SmashError("prepare_reads: max_len must be 1..255")
+        a = np.zeros((len(seqs), max_len), np.uint8)
+        for i, q in enumerate(seqs):
+            q = bytes(q)
+            if len(q) > max_len:
+                raise SmashError("prepare_reads: read %d has %d bases, max_len is %d"
+                                 % (i, len(q), max_len))
+            if 0 in q:
+                raise SmashError("prepare_reads: read %d holds a zero byte" % i)
+            a[i, :len(q)] = np.frombuffer(q, np.uint8)
+        a[a == ord("N")] = ord("Z")
+        return _LOWER[a]   # (0 stays 0)
     a = np.asarray(seqs, np.uint8).copy()
     a[a == ord("N")] = ord("Z")
     return _LOWER[a]
@@ -476,7 +497,7 @@ def pipeline_max_batch(read_len, min_len=20):
 
 def to_rows(d_reads, read_len=None):
     """a [2n, L] uint8 device tensor of mates as the native rows [2n, stride]
-    (zero padded)"""
+    (zero padded; zero-padded mates of mixed lengths stay what they are)"""
     import torch
     L = read_len or d_reads.shape[1]
     rows = torch.zeros((d_reads.shape[0], read_stride(L)), dtype=torch.uint8, device=d_reads.device)
@@ -494,7 +515,7 @@ class Pipeline:
 
     def __init__(self, index: Index, chrom_sizes: dict, bin_starts, read_len,
                  max_pairs, min_len=20, min_excess=4, hit_window=10000,
-                 dedup_capacity=None, read_stride=0):
+                 dedup_capacity=None, read_stride=0, var_len=False):
         self.index = index
         sizes = index.contig_sizes
         self.tag, self.small, self.off = contig_tables(index.contigs, sizes, chrom_sizes)
@@ -512,6 +533,17 @@ class Pipeline:
         self.stride = read_stride or read_len
         self.max_pairs = max_pairs
         self.slots = read_len - min_len + 1
+        self.var_len = False
+        if var_len:
+            self.set_var_len(True)
+
+    def set_var_len(self, on=True):
+        """variable-length mode (smash_pipeline_var_len): a mate's length is
+        the offset of the first zero byte of its row, read_len the longest a
+        mate can be (prepare_reads(list, max_len) builds such rows); between
+        runs only"""
+        check(lib().smash_pipeline_var_len(self.h, 1 if on else 0), "smash_pipeline_var_len")
+        self.var_len = bool(on)
 
     def count_batch(self, d_reads, n_pairs, d_counts, stream=None):
         """d_reads: device uint8 [2*n_pairs, read_len] (torch tensor or ptr)."""
@@ -710,6 +742,13 @@ class Pipeline:
                                         _p(hits, u64p), None), "smash_pipeline_peek")
         return nk, keep, hits.reshape(n_pairs, 2 * self.slots)
 
+    def peek_lens(self, n_pairs):
+        """the last batch's 2 * n_pairs mate lengths as the device took them"""
+        lens = np.zeros(2 * n_pairs, np.uint16)
+        check(lib().smash_pipeline_peek_lens(self.h, _p(lens, C.POINTER(C.c_uint16))),
+              "smash_pipeline_peek_lens")
+        return lens
+
     def close(self):
         """free the pipeline's device buffers now (its streams are
         synchronised first); the object is unusable afterwards"""
@@ -746,10 +785,11 @@ def _ptr(x):
 
 
 def map_batch(index: Index, d_reads, n_reads, read_len, d_out, cap, d_n, min_len=20,
-              stream=None, mode=SMASH_MODE_MAM):
-    """longSA::MAM over a batch (smash_map_batch)."""
+              stream=None, mode=SMASH_MODE_MAM, d_lens=None):
+    """longSA::MAM over a batch (smash_map_batch).  d_lens: a device uint16
+    length per read (rows of read_len bytes, each read at its row's start)."""
     check(lib().smash_map_batch(index.h, mode, min_len, _ptr(d_reads),
-                                read_len, None, read_len, n_reads, _ptr(d_out), cap,
+                                read_len, _ptr(d_lens), read_len, n_reads, _ptr(d_out), cap,
                                 _ptr(d_n), vp(_stream(stream))), "smash_map_batch")
 
 
@@ -894,16 +934,18 @@ def sam_format(contigs, h_rec, h_n, cap, names, seqs, quals=None, optionals=None
 
 
 def sam_records(index: Index, d_reads, n, read_len, cap, tag_offsets=None, min_len=20,
-                stream=None):
+                stream=None, d_lens=None):
     """MAM search + per-match records on the device (smash_map_batch ->
     smash_sam_records_packed); returns host copies (SAM_REC[sum(counts)] packed
     read after read, counts[n]).  The record table is sized by the matches
-    found (an exclusive scan of the counts), not by n * cap."""
+    found (an exclusive scan of the counts), not by n * cap.  d_lens: a device
+    uint16 length per read, in rows of read_len >= 255 bytes."""
     import torch
     dev = d_reads.device
     d_m = torch.empty(n * cap, dtype=torch.int64, device=dev)
     d_n = torch.empty(n, dtype=torch.int32, device=dev)
-    map_batch(index, d_reads, n, read_len, d_m, cap, d_n, min_len=min_len, stream=stream)
+    map_batch(index, d_reads, n, read_len, d_m, cap, d_n, min_len=min_len, stream=stream,
+              d_lens=d_lens)
     cnt = d_n.to(torch.int64).clamp_(max=cap)
     d_off = torch.cumsum(cnt, 0) - cnt
     total = int(cnt.sum().item()) if n else 0
@@ -911,7 +953,7 @@ def sam_records(index: Index, d_reads, n, read_len, cap, tag_offsets=None, min_l
     d_tag = None
     if tag_offsets is not None:
         d_tag = torch.from_numpy(np.ascontiguousarray(tag_offsets, np.uint32).view(np.int32)).to(dev)
-    check(lib().smash_sam_records_packed(index.h, _ptr(d_reads), read_len, None, read_len, n, _ptr(d_m),
+    check(lib().smash_sam_records_packed(index.h, _ptr(d_reads), read_len, _ptr(d_lens), read_len, n, _ptr(d_m),
                                          cap, _ptr(d_n), _ptr(d_off), _ptr(d_tag), _ptr(d_rec),
                                          vp(_stream(stream))),
           "smash_sam_records_packed")
@@ -923,35 +965,51 @@ def sam_records(index: Index, d_reads, n, read_len, cap, tag_offsets=None, min_l
 
 
 def sam_lines(index: Index, d_reads, read_len, names, seqs, quals=None, optionals=None,
-              nomap=True, tag_offsets=None, small_chr=None, cap=None, min_len=20, stream=None):
+              nomap=True, tag_offsets=None, small_chr=None, cap=None, min_len=20, stream=None,
+              lens=None):
     """memsam `-rcref -samin -samout [-nomap]` lines for 2n mates (read 1, read 2 of
     each pair, names with the ':0'/':1' suffix of query.cpp:641-642): the MAM search
     (smash_map_batch), the per-match records on the device (smash_sam_records) and
     the host formatting of print_matches (query.cpp:331-415).  With tag_offsets
     (u32 sam_header offsets per forward contig) the mappability_tag L/R columns
-    are appended (mappability_tag.cpp:93-124).  Returns (bytes, tag_error)."""
+    are appended (mappability_tag.cpp:93-124).  Returns (bytes, tag_error).
+    lens: the reads' own lengths (mixed): d_reads is then [2n, read_len >= 255]
+    with each read at its row's start."""
     n = len(names)
+    d_lens = None
+    if lens is not None:
+        import torch
+        lens = np.ascontiguousarray(lens, np.uint16)
+        if len(lens) != n or read_len < 255 or (n and int(lens.max()) > 255):
+            raise SmashError("sam_lines: one length (<= 255) per read, rows of >= 255 bytes")
+        d_lens = torch.from_numpy(lens.view(np.int16)).to(d_reads.device)
+    if cap is None and lens is not None:
+        cap = max(1, (int(lens.max()) if n else 0) - min_len + 1)
     if cap is None:
         cap = read_len - min_len + 1
-    h_rec, h_n = sam_records(index, d_reads, n, read_len, cap, tag_offsets, min_len, stream)
+    h_rec, h_n = sam_records(index, d_reads, n, read_len, cap, tag_offsets, min_len, stream,
+                             d_lens=d_lens)
     return sam_format(index.contigs, h_rec, h_n, SAM_PACKED | cap, names, seqs, quals, optionals,
                       nomap, tag_offsets is not None, small_chr)
 
 
-def read_fastq_pairs(r1_paths, r2_paths, batch_pairs=1 << 20, name_stride=64):
+def read_fastq_pairs(r1_paths, r2_paths, batch_pairs=1 << 20, name_stride=64, read_len=0):
     """All pairs of the two FASTQ lists through the native reader
     (smash_fastq_*): (names[n] as a fixed-width bytes array, reads[2n, L] u8
-    after replaceN + lowercasing), in file order."""
+    after replaceN + lowercasing), in file order.  read_len: 0 (the first
+    pair's length, which every mate must have), a required length, or
+    SMASH_LEN_VAR | M: mates of 1..M bases in zero-padded rows of M bytes."""
     arr1 = _cstrs([p.encode() for p in r1_paths])
     arr2 = _cstrs([p.encode() for p in r2_paths])
     h = vp()
     check(lib().smash_fastq_open(arr1, len(r1_paths), arr2, len(r2_paths), C.byref(h)),
           "smash_fastq_open")
     try:
-        L = C.c_uint32(0)
+        L = C.c_uint32(read_len)
         reads, names = [], []
         while True:
-            cap_len = L.value or 255
+            cap_len = (L.value & ~SMASH_LEN_VAR) or 255
+            L = C.c_uint32(L.value | (read_len & SMASH_LEN_VAR))   # (cleared on return)
             rb = np.empty(2 * batch_pairs * cap_len, np.uint8)
             nb = np.zeros(batch_pairs, "S%d" % name_stride)
             n = C.c_uint64()
@@ -972,7 +1030,9 @@ def read_fastq_pairs(r1_paths, r2_paths, batch_pairs=1 << 20, name_stride=64):
 
 def read_fastq_pairs_parallel(r1_paths, r2_paths, threads=0, name_stride=64, read_len=0):
     """read_fastq_pairs through the parallel reader (smash_fastq_read_parallel):
-    strict 4-line FASTQ only (SmashError SMASH_ERR_UNSUPPORTED otherwise)."""
+    strict 4-line FASTQ only (SmashError SMASH_ERR_UNSUPPORTED otherwise).
+    read_len as read_fastq_pairs', and SMASH_LEN_VAR alone: rows as wide as
+    the input's longest mate."""
     arr1 = _cstrs([os.fsencode(p) for p in r1_paths])
     arr2 = _cstrs([os.fsencode(p) for p in r2_paths])
     T = threads or min(16, os.cpu_count() or 1)
@@ -984,6 +1044,8 @@ def read_fastq_pairs_parallel(r1_paths, r2_paths, threads=0, name_stride=64, rea
     k = n.value
     rb = np.empty((2 * max(k, 1), max(L.value, 1)), np.uint8)
     nb = np.zeros(max(k, 1), "S%d" % name_stride)
+    W = L.value                                            # (the first call returned the width)
+    L = C.c_uint32(W | (read_len & SMASH_LEN_VAR))
     check(lib().smash_fastq_read_parallel(arr1, len(r1_paths), arr2, len(r2_paths), T, C.byref(L),
                                           k, _p(rb, vp), _p(nb, vp), name_stride, C.byref(n)),
           "smash_fastq_read_parallel")
@@ -996,7 +1058,9 @@ class FastqIndex:
     """Both FASTQ lists indexed once by the parallel reader
     (smash_fastq_index_*): .n pairs of .L bases in samtools sort -n order;
     pack(k0, k1, out) fills a [2 (k1 - k0), L] uint8 array (or a pinned CPU
-    tensor) with planned pairs [k0, k1).  Strict 4-line FASTQ only."""
+    tensor) with planned pairs [k0, k1).  Strict 4-line FASTQ only.
+    read_len = SMASH_LEN_VAR | M (M = 0: the longest mate): mixed lengths,
+    .L = the row width, every row zero padded past its mate."""
 
     def __init__(self, r1_paths, r2_paths, threads=0, read_len=0, sort_names=False):
         a1 = _cstrs([os.fsencode(p) for p in r1_paths])

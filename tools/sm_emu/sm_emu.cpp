@@ -208,12 +208,13 @@ using namespace smash;
 // the records of n reads, by k_prep (one lane per block, LDS image) or by
 // k_prep_direct (every (read, group) item, 256-thread blocks), as the device
 // default (mam.hip) does
+// (glen: the length the geometry g was made for)
 static int prep_records(const uint8_t *reads, uint64_t stride, const uint16_t *lens, uint32_t L,
                         uint64_t n, const uint64_t *in_text, const sm::Geom &g, uint32_t *rec,
-                        bool direct) {
+                        bool direct, uint32_t glen) {
   if (direct) {
     blockDim.x = 256;
-    const uint32_t ga = sm::prep_groups(lens ? 255 : L);
+    const uint32_t ga = sm::prep_groups(glen);
     const uint64_t items = n * ga;
     for (uint64_t i = 0; i < items; ++i) {
       blockIdx.x = unsigned(i / 256);
@@ -246,10 +247,16 @@ extern "C" int sm_emu_prep(const uint8_t *reads, uint64_t stride, const uint16_t
   const sm::Geom g = sm::make_geom(lens ? 255 : L);
   const uint64_t words = n * g.chunks * 4;
   for (uint64_t i = 0; i < words; ++i) out_lds[i] = out_direct[i] = 0xDEADBEEFu;   // all written?
-  if (prep_records(reads, stride, lens, L, n, in_text, g, out_lds, false)) return -1;
-  if (prep_records(reads, stride, lens, L, n, in_text, g, out_direct, true)) return -1;
+  if (prep_records(reads, stride, lens, L, n, in_text, g, out_lds, false, lens ? 255 : L)) return -1;
+  if (prep_records(reads, stride, lens, L, n, in_text, g, out_direct, true, lens ? 255 : L)) return -1;
   return int(g.chunks * 4);
 }
+
+// per-read lengths of the next sm_emu_map calls (null: every read has L
+// bases): the variable-length pipeline's search -- records built with the
+// lengths in the geometry of L, the longest read, never direct rows
+static const uint16_t *emu_lens = nullptr;
+extern "C" void sm_emu_set_lens(const uint16_t *lens) { emu_lens = lens; }
 
 template <class IdxT>
 static int run(const uint8_t *T, const void *SA, const void *ISA, const uint8_t *L8,
@@ -262,7 +269,9 @@ static int run(const uint8_t *T, const void *SA, const void *ISA, const uint8_t 
   if (g.w_row > sizeof(sm::ldsw) / 4) return -1;
   // direct rows (the device's path for native-row input, the default here as
   // in bench.py; SMASH_SM_DIRECT=0: records built by k_prep)
-  const bool direct = !(std::getenv("SMASH_SM_DIRECT") && std::getenv("SMASH_SM_DIRECT")[0] == '0');
+  const uint16_t *lens = emu_lens;
+  const bool direct = !lens &&
+                      !(std::getenv("SMASH_SM_DIRECT") && std::getenv("SMASH_SM_DIRECT")[0] == '0');
   const uint64_t rw = 4ull * g.w_row;   // native row bytes
   std::vector<uint4> rows_mem(direct ? n * rw / 16 + 4 : 0);
   uint8_t *rows_p = direct ? reinterpret_cast<uint8_t *>(rows_mem.data()) : nullptr;
@@ -278,8 +287,8 @@ static int run(const uint8_t *T, const void *SA, const void *ISA, const uint8_t 
   struct { uint4 *p; size_t n; uint4 *data() { return p; } size_t size() const { return n; } } rec{
       rec_p, size_t(n * g.chunks)};
   if (!direct &&
-      prep_records(reads, stride, nullptr, L, n, in_text, g, reinterpret_cast<uint32_t *>(rec.data()),
-                   !(std::getenv("SMASH_PREP_LDS") && std::getenv("SMASH_PREP_LDS")[0] == '1')))
+      prep_records(reads, stride, lens, L, n, in_text, g, reinterpret_cast<uint32_t *>(rec.data()),
+                   !(std::getenv("SMASH_PREP_LDS") && std::getenv("SMASH_PREP_LDS")[0] == '1'), L))
     return -1;
   threadIdx.x = 0;
   sm::Ctx<IdxT> c;
@@ -300,7 +309,7 @@ static int run(const uint8_t *T, const void *SA, const void *ISA, const uint8_t 
   c.pf = std::getenv("SMASH_SM_PF") ? uint32_t(std::atoi(std::getenv("SMASH_SM_PF"))) : 1;
   c.u32 = std::getenv("SMASH_SM_U32") ? uint32_t(std::atoi(std::getenv("SMASH_SM_U32"))) : 1;
   c.f2 = std::getenv("SMASH_SM_F2") ? uint32_t(std::atoi(std::getenv("SMASH_SM_F2"))) : 2;
-  c.lens = nullptr; c.len0 = L; c.cap = cap; c.n_reads = n;
+  c.lens = lens; c.len0 = L; c.cap = cap; c.n_reads = n;
   c.out = out; c.n_out = n_out;
   unsigned long long work = 0;
   c.work = &work;

@@ -144,11 +144,18 @@ class Emu:
         self.it = in_text_words(list(ix.acc.in_text))
         self.isz = np.dtype(it).itemsize
 
-    def map(self, reads, min_len=20, cap=512, lin_blocks=8):   # = the device default (mam.hip)
-        """reads: uint8 [n, L].  Returns (list of [(ref, q, len)], iterations);
-        self.counters: {array: (16-byte probes, 64-byte line transitions)}."""
+    def map(self, reads, min_len=20, cap=512, lin_blocks=8, lens=None):   # = the device default (mam.hip)
+        """reads: uint8 [n, L]; lens: uint16 [n], each read's own length (its
+        row zero padded past it), as the variable-length pipeline searches:
+        through records in the geometry of L.  Returns (list of [(ref, q,
+        len)], iterations); self.counters: {array: (16-byte probes, 64-byte
+        line transitions)}."""
         reads = np.ascontiguousarray(reads, np.uint8)
         n, L = reads.shape
+        if lens is not None:
+            lens = np.ascontiguousarray(lens, np.uint16)
+            assert lens.shape == (n,) and (n == 0 or int(lens.max()) <= L)
+        lib().sm_emu_set_lens(lens.ctypes.data_as(C.c_void_p) if lens is not None else None)
         out = np.zeros(n * cap, np.uint64)
         nout = np.zeros(n, np.uint32)
         iters = np.zeros(n, np.uint32)
@@ -167,6 +174,7 @@ class Emu:
             nout.ctypes.data_as(C.c_void_p), iters.ctypes.data_as(C.c_void_p),
             spans.ctypes.data_as(C.c_void_p), viol.ctypes.data_as(C.c_void_p),
             C.c_uint32(lin_blocks), ctr.ctypes.data_as(C.c_void_p), C.c_int(int(self.packed)))
+        lib().sm_emu_set_lens(None)
         assert rc == 0
         assert viol[0] == 0, ("out-of-range probe", viol.tolist())
         res = []
