@@ -151,6 +151,51 @@ int smash_index_query(const smash_index *ix, smash_index_info *out);
  * Synchronous; no search may run on the index meanwhile. */
 int smash_index_pack(smash_index *ix, int pack, void *stream);
 
+/* ---- index verification (csrc/verify.hip) ----------- */
+/* A complete proof, on the device, that the resident arrays are THE index of
+ * the resident text: nothing is sampled and the SA proof does not go through
+ * the LCP array.  Every value taken from SA, ISA, the LCP bytes or the
+ * overflow table is range-checked before it indexes anything, so the checks
+ * are safe on arrays of any content (a stale, damaged or foreign cache).   */
+#define SMASH_VERIFY_LAYOUT 1u   /* contig table vs text, rc halves            */
+#define SMASH_VERIFY_SA     2u   /* perm + order: SA is THE suffix array, ISA its inverse */
+#define SMASH_VERIFY_LCP    4u   /* every LCP value exact + overflow table well-formed */
+#define SMASH_VERIFY_MAP    8u   /* d_map equals the map recomputed from the index */
+#define SMASH_VERIFY_ALL   15u
+typedef struct {
+  uint64_t layout_bad, layout_first;
+  uint64_t perm_bad,   perm_first;
+  uint64_t order_bad,  order_first;
+  uint64_t lcp_bad,    lcp_first;
+  uint64_t ovf_bad,    ovf_first;
+  uint64_t map_bad,    map_first;      /* *_first: smallest bad rank (perm, order,
+                                          lcp), text position (layout), table
+                                          entry (ovf) or map.bin byte offset (map);
+                                          ~0 if none */
+  uint64_t n_lcp255;                   /* ranks with L8 == 255 (must equal n_lcp_overflow) */
+  uint64_t lcp_irreducible;            /* ranks proven by direct comparison */
+  uint64_t lcp_bytes_compared;         /* bytes of text those comparisons read, per side */
+  uint64_t lcp_longest;                /* longest single comparison */
+  uint32_t checked;                    /* flags that ran */
+  uint32_t ok;                         /* 1: every check that ran found nothing */
+  double seconds;
+} smash_verify_report;
+/* Read-only and synchronous; any index (created or loaded, 4- or 8-byte
+ * elements, packed or plain words, either layout).  SMASH_OK whenever the
+ * checks ran: the verdict is out->ok.  SMASH_VERIFY_MAP recomputes the map
+ * with smash_mappability_scan, which trusts the arrays: it runs only when
+ * LAYOUT, SA and LCP ran in the same call and found nothing, and is skipped
+ * (not an error; see out->checked) otherwise or when the index has no map. */
+int smash_index_verify(const smash_index *ix, uint32_t flags, smash_verify_report *out, void *stream);
+/* smash_index_load_layout with a gate: LAYOUT | SA | LCP (mandatory in
+ * `flags`, else SMASH_ERR_ARG) run on the uploaded files before anything is
+ * derived from them; with SMASH_VERIFY_MAP a map.bin read from the file is
+ * rechecked once the arrays are proven.  On a finding everything is freed,
+ * *out is filled, smash_last_error names the first failing check with its
+ * rank or position, and SMASH_ERR_IO is returned with *out_ix untouched. */
+int smash_index_load_verified(const char *fasta_path, int rcref, int device, uint32_t flags,
+                              smash_verify_report *out, smash_index **out_ix);
+
 /* ========================================================================== */
 /* Search: replaces longSA::MAM(Aligner&) (longSA.cpp:503-536) for a batch   */
 /* (mode MAM / MAM_PLAIN; MUM as longSA::MUM, longSA.cpp:549-585).            */

@@ -107,6 +107,40 @@ struct IdxArr {
   __host__ __device__ uint64_t operator[](uint64_t i) const { return uint64_t(p[i]) & mask; }
 };
 
+// The complement of a text byte (fasta.cpp:26-60): the IUPAC codes with a
+// complement, either case; every other byte maps to itself.  One table for
+// the SAM writer's reverse complements (samout.hip) and the layout check of
+// the rc halves (verify.hip).
+__host__ __device__ inline uint8_t comp_base(uint8_t ch) {
+  switch (ch) {
+    case 'a': return 't';
+    case 'c': return 'g';
+    case 'g': return 'c';
+    case 't': return 'a';
+    case 'r': return 'y';
+    case 'y': return 'r';
+    case 'm': return 'k';
+    case 'k': return 'm';
+    case 'b': return 'v';
+    case 'd': return 'h';
+    case 'h': return 'd';
+    case 'v': return 'b';
+    case 'A': return 'T';
+    case 'C': return 'G';
+    case 'G': return 'C';
+    case 'T': return 'A';
+    case 'R': return 'Y';
+    case 'Y': return 'R';
+    case 'M': return 'K';
+    case 'K': return 'M';
+    case 'B': return 'V';
+    case 'D': return 'H';
+    case 'H': return 'D';
+    case 'V': return 'B';
+    default: return ch;
+  }
+}
+
 // Packed match (smash_gpu.h): ref 48 | qoff 8 | len 8
 __host__ __device__ inline uint64_t pack_match(uint64_t ref, uint32_t q,
                                                uint32_t len) {
@@ -212,6 +246,13 @@ int ensure_keys(smash_pipeline *p, uint64_t n_next, hipStream_t s);
 // work on s) instead of for everything on s (pipeline.hip)
 int count_batch_ev(smash_pipeline *p, const uint8_t *d_reads, uint64_t n_pairs,
                    uint64_t *d_counts, hipStream_t s, hipEvent_t in_ev);
+// verify.hip: smash_index_verify on stream s.  proven: LAYOUT, SA and LCP of
+// this index were found clean already (the gate of smash_index_load_verified),
+// so the map recheck may run without them in the same call
+int verify_impl(const smash_index *ix, uint32_t flags, smash_verify_report *out, hipStream_t s,
+                bool proven);
+// the first finding of a report as text ("" when it has none)
+std::string verify_finding(const smash_verify_report &r, uint64_t n_ovf);
 int probe_check(const smash_index *ix);   // synchronous; SMASH_OK or the probe error
 // mem.hip: smash_map_batch's MUM mode (MAM, then cleanMUMcand per read)
 int map_batch_mum(const smash_index *ix, uint32_t min_len, const uint8_t *seqs, uint64_t stride,

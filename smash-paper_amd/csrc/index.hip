@@ -180,12 +180,19 @@ extern "C" int smash_index_create(const uint8_t *h_text, uint64_t N, uint32_t n_
   return smash_index_create_layout(h_text, N, n_seq, h_startpos, h_sizes, names, 1, device, out);
 }
 
-extern "C" int smash_index_load_layout(const char *fasta_path, int rcref, int device,
-                                       smash_index **out) {
-  if (!fasta_path || !out) {
-    set_error("smash_index_load: bad arguments");
-    return SMASH_ERR_ARG;
-  }
+namespace {
+
+// a gate's finding: the load fails with SMASH_ERR_IO and this message
+struct verify_reject {
+  std::string what;
+};
+
+// smash_index_load_layout, and with vflags != 0 smash_index_load_verified:
+// the same load with the verifier (verify.hip) run on the uploaded files
+// before anything is derived from them, and on a map.bin read from the file
+// once they are proven
+int load_impl(const char *fasta_path, int rcref, int device, uint32_t vflags,
+              smash_verify_report *rep, smash_index **out) {
   const std::string dir = std::string(fasta_path) + ".bin/";
   const std::string rc = rcref ? "rc1" : "rc0";   // fasta.cpp:98, longSA.cpp:103
   std::vector<uint8_t> refhdr, idxhdr;
@@ -275,14 +282,39 @@ extern "C" int smash_index_load_layout(const char *fasta_path, int rcref, int de
       SMASH_HIPX(hipMemcpy(ix->d_ovf, ovf.data(), 8 * ovf.size(), hipMemcpyHostToDevice));
     }
     upload_tables(ix.get(), s);
+    const uint32_t proof = SMASH_VERIFY_LAYOUT | SMASH_VERIFY_SA | SMASH_VERIFY_LCP;
+    auto gate = [&](uint32_t flags, bool proven) {
+      smash_verify_report r;
+      const int rc = verify_impl(ix.get(), flags, &r, s, proven);
+      if (rc != SMASH_OK) throw hip_failure{smash_last_error()};
+      const double before = rep->seconds;
+      const uint32_t ran = rep->checked | r.checked;
+      if (proven) {   // the map's fields join the proof's
+        rep->map_bad = r.map_bad;
+        rep->map_first = r.map_first;
+        rep->ok = rep->ok && r.ok;
+      } else {
+        *rep = r;
+      }
+      rep->checked = ran;
+      rep->seconds = before + r.seconds;
+      if (!r.ok) {
+        (void)hipStreamDestroy(s);
+        throw verify_reject{"smash_index_load_verified: " + dir + " rejected: " +
+                            verify_finding(r, ix->n_ovf)};
+      }
+    };
+    if (vflags) gate(proof, false);
     uint64_t total = 0;
     for (uint32_t c = 0; c < ix->n_seq; c += 2) total += ix->sizes[c];
+    bool map_from_file = false;
     if (!ix->rcref) {
       // no map.bin for the forward-only layout (-mappability requires -rcref)
     } else if (read_file(dir + "map.bin", buf) && buf.size() == 2 + 2 * total) {
       ix->map_bytes = buf.size();
       ix->d_map = dalloc<uint8_t>(buf.size());
       SMASH_HIPX(hipMemcpy(ix->d_map, buf.data(), buf.size(), hipMemcpyHostToDevice));
+      map_from_file = true;
     } else {
       uint32_t *lcp = dalloc<uint32_t>(N);
       k_lcp_expand<<<grid_for(N, 256, 65536), 256, 0, s>>>(ix->d_lcp8, N, lcp);
@@ -294,6 +326,10 @@ extern "C" int smash_index_load_layout(const char *fasta_path, int rcref, int de
     }
     SMASH_HIPX(hipStreamSynchronize(s));
     build_aux(ix.get(), s);
+    if ((vflags & SMASH_VERIFY_MAP) && map_from_file) {
+      SMASH_HIPX(hipStreamSynchronize(s));
+      gate(SMASH_VERIFY_MAP, true);
+    }
     pack_index(ix.get(), true, s);
     SMASH_HIPX(hipStreamSynchronize(s));
     SMASH_HIPX(hipStreamDestroy(s));
@@ -302,9 +338,35 @@ extern "C" int smash_index_load_layout(const char *fasta_path, int rcref, int de
   } catch (hip_failure &f) {
     set_error(f.what);
     return f.what.find("hipMalloc") != std::string::npos ? SMASH_ERR_NOMEM : SMASH_ERR_IO;
+  } catch (verify_reject &f) {
+    set_error(f.what);
+    return SMASH_ERR_IO;
   }
   *out = ix.release();
   return SMASH_OK;
+}
+
+}  // namespace
+
+extern "C" int smash_index_load_layout(const char *fasta_path, int rcref, int device,
+                                       smash_index **out) {
+  if (!fasta_path || !out) {
+    set_error("smash_index_load: bad arguments");
+    return SMASH_ERR_ARG;
+  }
+  return load_impl(fasta_path, rcref, device, 0, nullptr, out);
+}
+
+extern "C" int smash_index_load_verified(const char *fasta_path, int rcref, int device,
+                                         uint32_t flags, smash_verify_report *rep,
+                                         smash_index **out) {
+  const uint32_t proof = SMASH_VERIFY_LAYOUT | SMASH_VERIFY_SA | SMASH_VERIFY_LCP;
+  if (!fasta_path || !out || !rep || (flags & proof) != proof || (flags & ~SMASH_VERIFY_ALL)) {
+    set_error("smash_index_load_verified: bad arguments (LAYOUT | SA | LCP are mandatory)");
+    return SMASH_ERR_ARG;
+  }
+  memset(rep, 0, sizeof(*rep));
+  return load_impl(fasta_path, rcref, device, flags, rep, out);
 }
 
 extern "C" int smash_index_load(const char *fasta_path, int device, smash_index **out) {

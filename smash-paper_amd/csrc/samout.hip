@@ -205,35 +205,7 @@ void prepare(Mate &m, const smash_sam_rec *rec, uint32_t n) {
 std::string rev_comp(const char *s) {   // fasta.cpp:26-60
   std::string o(s);
   std::reverse(o.begin(), o.end());
-  for (char &ch : o) {
-    switch (ch) {
-      case 'a': ch = 't'; break;
-      case 'c': ch = 'g'; break;
-      case 'g': ch = 'c'; break;
-      case 't': ch = 'a'; break;
-      case 'r': ch = 'y'; break;
-      case 'y': ch = 'r'; break;
-      case 'm': ch = 'k'; break;
-      case 'k': ch = 'm'; break;
-      case 'b': ch = 'v'; break;
-      case 'd': ch = 'h'; break;
-      case 'h': ch = 'd'; break;
-      case 'v': ch = 'b'; break;
-      case 'A': ch = 'T'; break;
-      case 'C': ch = 'G'; break;
-      case 'G': ch = 'C'; break;
-      case 'T': ch = 'A'; break;
-      case 'R': ch = 'Y'; break;
-      case 'Y': ch = 'R'; break;
-      case 'M': ch = 'K'; break;
-      case 'K': ch = 'M'; break;
-      case 'B': ch = 'V'; break;
-      case 'D': ch = 'H'; break;
-      case 'H': ch = 'D'; break;
-      case 'V': ch = 'B'; break;
-      default: break;
-    }
-  }
+  for (char &ch : o) ch = char(comp_base(uint8_t(ch)));
   return o;
 }
 

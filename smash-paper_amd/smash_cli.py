@@ -22,6 +22,11 @@ subcommand below takes the same inputs and writes the same files:
   search [-mum|-maxmatch] [-l N] REF.fa QUERY
                                 mummer's match triples for FASTA/FASTQ/SAM queries
                                 (one line per read: name, then ref,query,len)
+  verify [--no-map]             prove the REF.fa.bin/ cache on the device: text
+                                layout, SA / ISA, every LCP value, map.bin (one
+                                JSON report line; exit 1 when it is not the index
+                                of its text); map / count --verify: the same
+                                proof before the cache is used
 
 REF.fa comes from --ref or $SMASH_REF as in the scripts.  Every computation
 runs in libsmashgpu.so (include/smash_gpu.h); without it the commands fail.
@@ -217,11 +222,41 @@ def _ref(args):
     return ref
 
 
-def load_index(ref, device=0):
+def load_index(ref, device=0, verify=0):
+    """the REF.fa.bin/ cache when there is one, else the index built from the
+    FASTA.  verify (--verify): S.VERIFY_* flags for the cache, proven on the
+    device before it is used (an index built here needs no proof)"""
     if os.path.isdir(ref + ".bin") and any(
             os.path.exists(ref + ".bin/rc1.i%d.index.bin" % w) for w in (4, 8)):
-        return S.Index.load(ref, device=device)
+        try:
+            return S.Index.load(ref, device=device, verify=verify)
+        except S.SmashError as e:
+            if e.report is None:
+                raise
+            raise SystemExit(str(e)) from None
     return S.Index.from_fasta(ref, device=device)
+
+
+def _verify_flags(args):
+    return S.VERIFY_ALL if getattr(args, "verify", False) else 0
+
+
+def cmd_verify(args):
+    """prove REF.fa.bin/ on the device (smash_index_load_verified): the report
+    as one JSON line; exit 1 with the first finding on stderr when the cache
+    is not the index of its text"""
+    import json
+    ref = _ref(args)
+    flags = S.VERIFY_ALL & ~(S.VERIFY_MAP if args.no_map else 0)
+    try:
+        rep = S.Index.load(ref, device=args.device, verify=flags).verify_report
+    except S.SmashError as e:
+        if e.report is None:
+            raise SystemExit(str(e)) from None
+        print(json.dumps(e.report.as_dict()))
+        print(str(e), file=sys.stderr)
+        raise SystemExit(1) from None
+    print(json.dumps(rep.as_dict()))
 
 
 def cmd_index(args):
@@ -250,7 +285,7 @@ class _Run:
         import torch
         self.torch = torch
         self.ref = _ref(args)
-        self.ix = load_index(self.ref, args.device)
+        self.ix = load_index(self.ref, args.device, _verify_flags(args))
         cs_path = args.chrom_sizes or self.ref + ".bin/chrom_sizes.txt"
         self.cs = S.read_chrom_sizes(cs_path)
         if bins_path:
@@ -364,7 +399,7 @@ def _count_files(args, bins):
     name first unless --presorted)"""
     import torch
     ref = _ref(args)
-    ix = load_index(ref, args.device)
+    ix = load_index(ref, args.device, _verify_flags(args))
     cs = S.read_chrom_sizes(args.chrom_sizes or ref + ".bin/chrom_sizes.txt")
     rows, starts = S.read_bins(bins)
     r1, r2 = args.reads1.split(), args.reads2.split()
@@ -407,7 +442,7 @@ def _count_files_dist(args, bins, world):
     tdist.init_process_group("nccl", device_id=dev)
     cpu = tdist.new_group(backend="gloo")
     ref = _ref(args)
-    ix = load_index(ref, local)
+    ix = load_index(ref, local, _verify_flags(args))
     cs = S.read_chrom_sizes(args.chrom_sizes or ref + ".bin/chrom_sizes.txt")
     rows, starts = S.read_bins(bins)
     r1, r2 = args.reads1.split(), args.reads2.split()
@@ -657,6 +692,9 @@ def main(argv=None):
         p.add_argument("--sam", default=None, help="unmapped SAM input instead (mummer -samin)")
         p.add_argument("--chrom-sizes", default=None)
         p.add_argument("--batch", type=int, default=2_000_000, help="pairs per device batch")
+        p.add_argument("--verify", action="store_true",
+                       help="prove the REF.fa.bin/ cache on the device before using it "
+                            "(see the verify subcommand)")
         p.add_argument("--max-read-len", type=int, default=0, metavar="N",
                        help="mates of mixed lengths, each at most N bases (1..255; e.g. "
                             "adapter- or quality-trimmed reads); default: one length")
@@ -667,6 +705,10 @@ def main(argv=None):
                            help="distinct pair keys the de-dup set holds (0: sized from "
                                 "the input files)")
         p.set_defaults(fn=fn)
+    p = sub.add_parser("verify", help="prove REF.fa.bin/ (text layout, SA/ISA, LCP, map.bin) "
+                                      "on the device; one JSON report line, exit 1 if not clean")
+    p.add_argument("--no-map", action="store_true", help="skip the map.bin recheck")
+    p.set_defaults(fn=cmd_verify)
     p = sub.add_parser("varbin")
     for a in ("positions", "bins", "out", "stats", "chrom_sizes"):
         p.add_argument(a)

@@ -66,7 +66,15 @@ EXPORTS = [
     "smash_mappability_prepare", "smash_mappability_window", "smash_index_pack",
     "smash_pipeline_reserve_keys", "smash_pipeline_key_capacity", "smash_pipeline_error",
     "smash_mappability_release", "smash_pipeline_map_hints",
+    "smash_index_verify", "smash_index_load_verified",
 ]
+
+# smash_index_verify / Index.load(verify=...): the checks to run
+VERIFY_LAYOUT = 1   # contig table vs text, rc halves
+VERIFY_SA = 2       # SA is the suffix array of the text, ISA its inverse
+VERIFY_LCP = 4      # every LCP value exact, overflow table well-formed
+VERIFY_MAP = 8      # map.bin equals the map recomputed from the index
+VERIFY_ALL = 15
 
 
 class IndexInfo(C.Structure):
@@ -119,8 +127,26 @@ class Stats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class VerifyReport(C.Structure):
+    """smash_verify_report: per check the number of findings and the smallest
+    bad rank / text position / table entry / map.bin byte (~0: none)."""
+    _fields_ = [("layout_bad", C.c_uint64), ("layout_first", C.c_uint64),
+                ("perm_bad", C.c_uint64), ("perm_first", C.c_uint64),
+                ("order_bad", C.c_uint64), ("order_first", C.c_uint64),
+                ("lcp_bad", C.c_uint64), ("lcp_first", C.c_uint64),
+                ("ovf_bad", C.c_uint64), ("ovf_first", C.c_uint64),
+                ("map_bad", C.c_uint64), ("map_first", C.c_uint64),
+                ("n_lcp255", C.c_uint64), ("lcp_irreducible", C.c_uint64),
+                ("lcp_bytes_compared", C.c_uint64), ("lcp_longest", C.c_uint64),
+                ("checked", C.c_uint32), ("ok", C.c_uint32), ("seconds", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class SmashError(RuntimeError):
-    pass
+    """report: the VerifyReport of a load the verifier rejected (else None)"""
+    report = None
 
 
 _LIB = None
@@ -151,6 +177,9 @@ def lib():
                                             C.POINTER(vp)]
     L.smash_index_load.argtypes = [C.c_char_p, C.c_int, C.POINTER(vp)]
     L.smash_index_load_layout.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(vp)]
+    L.smash_index_verify.argtypes = [vp, C.c_uint32, C.POINTER(VerifyReport), vp]
+    L.smash_index_load_verified.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_uint32,
+                                            C.POINTER(VerifyReport), C.POINTER(vp)]
     L.smash_index_save.argtypes = [vp, C.c_char_p, C.c_uint64]
     L.smash_index_free.argtypes = [vp]
     L.smash_index_free.restype = None
@@ -383,12 +412,35 @@ class Index:
         return cls.create(*text_from_contigs(contigs), device=device)
 
     @classmethod
-    def load(cls, fasta_path, device=0, rcref=True):
-        """Load the reference's <fasta>.bin/ cache (longSA.cpp:100-136)."""
+    def load(cls, fasta_path, device=0, rcref=True, verify=0):
+        """Load the reference's <fasta>.bin/ cache (longSA.cpp:100-136).
+        verify: VERIFY_* flags (LAYOUT | SA | LCP at least) to prove the files
+        on the device before anything is built from them
+        (smash_index_load_verified); a rejected cache raises SmashError with
+        .code SMASH_ERR_IO (-3) and the findings in .report; the report of an
+        accepted one is the index's verify_report."""
         h = vp()
-        check(lib().smash_index_load_layout(fasta_path.encode(), 1 if rcref else 0, device,
-                                            C.byref(h)),
-              "smash_index_load")
+        rep = None
+        if verify:
+            rep = VerifyReport()
+            rc = lib().smash_index_load_verified(fasta_path.encode(), 1 if rcref else 0, device,
+                                                 verify, C.byref(rep), C.byref(h))
+            if rc != 0:
+                msg = lib().smash_last_error().decode(errors="replace")
+                e = SmashError("smash_index_load_verified failed (%d): %s" % (rc, msg))
+                e.code = rc
+                e.report = rep if rep.checked else None
+                raise e
+        else:
+            check(lib().smash_index_load_layout(fasta_path.encode(), 1 if rcref else 0, device,
+                                                C.byref(h)),
+                  "smash_index_load")
+        ix = cls._loaded(h, fasta_path, rcref)
+        ix.verify_report = rep
+        return ix
+
+    @classmethod
+    def _loaded(cls, h, fasta_path, rcref):
         names, sizes = [], []
         with open(fasta_path + ".bin/rc%d.ref.bin" % (1 if rcref else 0), "rb") as f:
             b = f.read()
@@ -400,6 +452,18 @@ class Index:
             names.append(b[off + 24:off + 24 + L].decode())
             off += 24 + L
         return cls(h.value, names, sizes)
+
+    verify_report = None   # Index.load(verify=...): the accepted cache's report
+
+    def verify(self, flags=VERIFY_ALL, stream=None):
+        """smash_index_verify: prove the resident arrays against the resident
+        text (read-only, synchronous).  Returns the VerifyReport; its ok is
+        the verdict, its checked the flags that ran (MAP is skipped for an
+        index without a map, and unless LAYOUT, SA and LCP ran clean)."""
+        rep = VerifyReport()
+        check(lib().smash_index_verify(self.h, flags, C.byref(rep), vp(_stream(stream))),
+              "smash_index_verify")
+        return rep
 
     def save(self, fasta_path, fasta_size=None):
         if fasta_size is None:
