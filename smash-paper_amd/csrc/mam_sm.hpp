@@ -1,7 +1,8 @@
 // smash-paper_amd/csrc/mam_sm.hpp -- the v3 MAM search as a lane state
-// machine: every loop iteration issues one 16-byte gather per lane (two for
-// the states that own two independent probes), then each lane advances its
-// state with ALU work only until it names its next address.
+// machine: every loop iteration issues the lanes' gathers back to back (one
+// 16-byte probe per lane, a second block for the states that own two
+// independent probes, a prefetched SA element), waits for them once, then each
+// lane advances its state with ALU work only until it names its next address.
 //
 // Why: a direct per-lane implementation (mam_read_v3, mam_device.hpp) keeps
 // the lanes of a wave in different phases; SIMT then issues each phase's
@@ -111,11 +112,25 @@
 namespace smash {
 namespace sm {
 
+// (through a global-address-space pointer to a 1-byte-aligned block: one
+// global_load_dwordx4.  A pointer cast from the integer alone is a generic
+// one, and its flat_load counts in lgkmcnt too, which ties the waits for the
+// LDS row to the gathers in flight)
+#ifdef SM_DMA_ROW_HOST
 __device__ __forceinline__ uint4 load16u(uint64_t a) {
   uint4 v;
   __builtin_memcpy(&v, reinterpret_cast<const uint8_t *>(a), 16);
   return v;
 }
+#else
+typedef uint32_t sm_u32x4 __attribute__((ext_vector_type(4)));
+typedef sm_u32x4 sm_u32x4_u __attribute__((aligned(1)));
+typedef __attribute__((address_space(1))) const sm_u32x4_u glb_block16_t;
+__device__ __forceinline__ uint4 load16u(uint64_t a) {
+  const sm_u32x4 b = *reinterpret_cast<glb_block16_t *>(a);
+  return make_uint4(b.x, b.y, b.z, b.w);
+}
+#endif
 
 #ifndef SM_DMA_ROW_HOST
 typedef __attribute__((address_space(3))) void lds_void_t;
@@ -649,8 +664,9 @@ inline void bad_table(const uint64_t in_text[4], uint32_t *lo, uint32_t *hi) {
   *hi = uint32_t(t[4]) | uint32_t(t[5]) << 8 | uint32_t(t[6]) << 16 | uint32_t(t[7]) << 24;
 }
 
-// One lane = one read at a time.  Each iteration: (1) the lanes with a
-// pending probe load 16 bytes (two blocks when need2); (2) "consume": the
+// One lane = one read at a time.  Each iteration: (1) every lane issues its
+// three loads (a lane without a pending probe reads a fixed dummy address
+// and sees zeros), followed by the iteration's one wait; (2) "consume": the
 // loaded block advances the lane's state; (3) "decide": a fixed chain of ALU
 // continuations names the next probe.  The chain has no loops: the two rare
 // transitions that go backwards in it (end of read inside traverse ->
@@ -841,20 +857,67 @@ __global__ __launch_bounds__(BLOCK, GEO ? SM_GEO_WPS : 1) void k_mam_sm(const Ct
     const uint64_t newm = __ballot(st == S_NEW);
     const uint32_t need = uint32_t(__popcll(newm));
     const uint64_t avail = q_end - q_next;
-    unsigned long long base = 0;
-    uint32_t take = 0;
-    if (newm && avail < need) {
-      take = need > SM_KNOB(grab, 16u) ? need : SM_KNOB(grab, 16u);
-      if (lane == uint32_t(__builtin_ctzll(newm)))
-        base = atomicAdd(c.work, (unsigned long long)take);
-    }
     const uint64_t live = __ballot(st != S_EXIT);
     if (live == 0) break;
     if (STATS) { w_iters += 1; w_active += __popcll(live); }
+    const uint32_t st_ld = S_COPY + gDirect;   // the lowest state that loads
+    if (CHECK && st >= st_ld &&
+        (addr < c.lo || addr >= c.hi || (need2 && (addr2 < c.lo || addr2 >= c.hi)))) {
+      if (atomicAdd(c.viol, 1ull) == 0) {
+        c.viol[1] = st; c.viol[2] = op; c.viol[3] = addr; c.viol[4] = need2 ? addr2 : 0;
+        c.viol[5] = prefix; c.viol[6] = depth; c.viol[7] = start; c.viol[8] = end; c.viol[9] = rd;
+      }
+      st = S_EXIT;
+      need2 = false; pfr = false;
+    }
+    // The iteration's gathers.  The order below is what keeps one memory
+    // round trip per iteration: the gathers are issued first, back to back,
+    // with nothing waited for ahead of them; one wait follows; everything
+    // that reads memory results (the rows DMA'd last iteration, the claim)
+    // comes after it.
+    const bool ld1 = st >= st_ld, ld2 = need2, ld3 = pfr;
+    const uint64_t amask = st >= S_BYTE ? ~uint64_t(0) : ~uint64_t(15);
+    const uint64_t a1 = addr & amask, a2 = addr2 & (pf ? ~uint64_t(15) : amask);
+    const uint64_t i3 = (m + 1 + hi) >> 1;
+    uint4 v, v2;
+    uint64_t v3;
+    unsigned long long base = 0;
+    uint32_t take = 0;
+    if (newm && avail < need) take = need > SM_KNOB(grab, 16u) ? need : SM_KNOB(grab, 16u);
+#ifdef SM_HOST_LANE
+    // (the emulated lane issues, checks and counts its real probes only)
+    v = ld1 ? SM_LOAD16ST(a1, st) : make_uint4(0, 0, 0, 0);
+    v2 = !ld2 ? make_uint4(0, 0, 0, 0) : pf ? SM_LOADPF16(a2) : SM_LOAD16ST(a2, st);
+    v3 = ld3 ? SM_LOADIDX(c.SA, i3) : 0;
+#else
+    // Every lane loads all three, no exec-mask block and no merge copy (a
+    // conditional load's copy into the zero-initialised register made the
+    // compiler wait for v inside its block, before v2 and v3 were issued).
+    // A lane with nothing to load reads the first block of the text / SA[0]:
+    // always mapped, inside [c.lo, c.hi), and the wave's idle lanes share one
+    // hot line.  Lanes that did not load see zeros, as several consumers
+    // expect.
+    const uint64_t idle = reinterpret_cast<uint64_t>(c.T);
+    v = SM_LOAD16ST(ld1 ? a1 : idle, st);
+    v2 = SM_LOAD16(ld2 ? a2 : idle);
+    v3 = SM_LOADIDX(c.SA, ld3 ? i3 : 0);
+#endif
+    // the claim's atomic goes out behind the gathers: its return is needed
+    // only where the reads are assigned, below
+    if (take && lane == uint32_t(__builtin_ctzll(newm)))
+      base = atomicAdd(c.work, (unsigned long long)take);
+#ifndef SM_HOST_LANE
+    // the one wait: vmcnt retires in order, so this also covers the rows
+    // DMA'd in the previous iteration and its match stores
+    __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
+    asm volatile("" ::: "memory");        // (LDS rows written by the DMA are read below)
+    if (!ld1) v = make_uint4(0, 0, 0, 0);
+    if (!ld2) v2 = make_uint4(0, 0, 0, 0);
+    if (!ld3) v3 = 0;
+#endif
     // direct rows: the rows DMA'd last iteration (the lanes still in S_COPY)
-    // have landed -- waited for here, before this iteration's loads are
-    // issued, where nothing else is outstanding; the bad mask of each, one
-    // row word per lane, assembled only when a base is bad
+    // have landed; the bad mask of each, one row word per lane, assembled
+    // only when a base is bad
     if (gDirect) {
       uint64_t cm = __ballot(st == S_COPY);
       if (cm) {
@@ -862,7 +925,6 @@ __global__ __launch_bounds__(BLOCK, GEO ? SM_GEO_WPS : 1) void k_mam_sm(const Ct
 #ifdef SM_HOST_LANE
         if (st == S_COPY) bad = row_bad_mask(row, L, c.bad_tab_lo, c.bad_tab_hi);
 #else
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         while (cm) {
           const uint32_t ln = uint32_t(__builtin_ctzll(cm));
           cm &= cm - 1;
@@ -884,25 +946,6 @@ __global__ __launch_bounds__(BLOCK, GEO ? SM_GEO_WPS : 1) void k_mam_sm(const Ct
 #endif
       }
     }
-    const uint32_t st_ld = S_COPY + gDirect;   // the lowest state that loads
-    if (CHECK && st >= st_ld &&
-        (addr < c.lo || addr >= c.hi || (need2 && (addr2 < c.lo || addr2 >= c.hi)))) {
-      if (atomicAdd(c.viol, 1ull) == 0) {
-        c.viol[1] = st; c.viol[2] = op; c.viol[3] = addr; c.viol[4] = need2 ? addr2 : 0;
-        c.viol[5] = prefix; c.viol[6] = depth; c.viol[7] = start; c.viol[8] = end; c.viol[9] = rd;
-      }
-      st = S_EXIT;
-      need2 = false; pfr = false;
-    }
-    uint4 v = make_uint4(0, 0, 0, 0), v2 = make_uint4(0, 0, 0, 0);
-    uint64_t v3 = 0;
-    const uint64_t amask = st >= S_BYTE ? ~uint64_t(0) : ~uint64_t(15);
-    if (st >= st_ld) v = SM_LOAD16ST(addr & amask, st);
-    if (need2) {
-      if (pf) v2 = SM_LOADPF16(addr2 & ~uint64_t(15));
-      else v2 = SM_LOAD16ST(addr2 & amask, st);
-    }
-    if (pfr) v3 = SM_LOADIDX(c.SA, (m + 1 + hi) >> 1);
     bool fresh = false;   // assigned a read this iteration: its first chunk loads next
     if (newm) {
       if (take) base = __shfl(base, int(__builtin_ctzll(newm)), 64);
