@@ -174,9 +174,10 @@ int run_sm(const smash_index *ix, const sm::Ctx<IdxT> &c0, uint64_t n_reads, siz
         "consume", "S_ALU", "S_COPY", "S_BM", "S_KT", "S_IDX", "S_BYTE", "S_CMP", "S_USCAN",
         "S_EX", "A_BS", "A_BS_DONE", "A_XL_DONE", "A_RUN_DONE", "A_CHAIN_DONE", "A_EXPAND",
         "A_AFTER", "A_TOP", "A_TRAV", "A_DONE", "TOP.!clean", "TOP.codes1", "TOP.codes2",
-        "TOP.kt", "TOP.filter", "TOP.kcache", "dma", "rowbad"};
+        "TOP.kt", "TOP.filter", "TOP.kcache", "dma", "rowbad", "A_BSP", "A_EXS", "A_EMIT",
+        "TOP.reset"};
     std::fprintf(stderr, "[k_mam_sm] wave iterations running each region (%%):");
-    for (int k = 0; k < 28; ++k)
+    for (int k = 0; k < 32; ++k)
       if (ws[64 + k])
         std::fprintf(stderr, " %s %.1f", regions[k], 100.0 * double(ws[64 + k]) / double(ws[0] ? ws[0] : 1));
     std::fprintf(stderr, "\n");

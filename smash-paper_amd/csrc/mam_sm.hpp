@@ -94,7 +94,9 @@
 
 // STATS builds: count the wave iterations in which a code region runs (any
 // lane active in it), wave_stats[64 + k]; the regions' costs are paid per
-// such iteration (tools/isa_regions.py gives their static VALU)
+// such iteration (tools/isa_regions.py gives their static VALU).  The host
+// emulation substitutes its own: the blocks a lane enters, in order
+#ifndef SM_REGION
 #define SM_REGION(k)                                                              \
   do {                                                                            \
     if (STATS) {                                                                  \
@@ -102,6 +104,7 @@
       if (lane == uint32_t(__builtin_ctzll(am_))) atomicAdd(c.wave_stats + 64 + (k), 1ull); \
     }                                                                             \
   } while (0)
+#endif
 
 // n 16-byte record chunks from src into the LDS row dst, asynchronously
 // (LDS-DMA: lanes 0..n-1 each move one chunk; dst wave-uniform)
@@ -367,7 +370,11 @@ enum : uint32_t { O_SAPOS, O_SAPOS2, O_BS_SA, O_ISAJ, O_NS_SA2, O_NS_ISA2 };
 enum : uint32_t { O_EXT = 0, O_BS };
 // ALU continuations, in the order the decide chain runs them
 enum : uint32_t { A_NONE = 0, A_BSP, A_BS, A_BS_DONE, A_XL_DONE, A_RUN_DONE, A_CHAIN_DONE,
-                  A_EXPAND, A_AFTER, A_TOP, A_TRAV, A_DONE, A_EMIT, A_EXS };
+                  A_EXPAND, A_AFTER, A_TOP, A_TRAV, A_DONE, A_EMIT, A_EXS,
+                  // A_TOP after the search state's reset to the root (depth 0,
+                  // the whole SA, no position): the reset stands once, at A_TOP's
+                  // entry, and not at each of the sites that ask for it
+                  A_TOPR };
 // binary-search modes: 0 where P' sorts (traverse); 1 / 2 the left / right
 // end of a run of suffixes sharing `cap` characters (from `cbase`) with P
 enum : uint32_t { BS_INSERT = 0, BS_LEFT, BS_RIGHT };
@@ -669,8 +676,8 @@ inline void bad_table(const uint64_t in_text[4], uint32_t *lo, uint32_t *hi) {
 // and sees zeros), followed by the iteration's one wait; (2) "consume": the
 // loaded block advances the lane's state; (3) "decide": a fixed chain of ALU
 // continuations names the next probe.  The chain has no loops: the two rare
-// transitions that go backwards in it (end of read inside traverse ->
-// after-traverse; a window filter skip -> the next window) park the lane in
+// transitions that go backwards in it (after-traverse at depth <= 1 -> the
+// root, A_TOPR; a window filter skip -> the next window) park the lane in
 // S_ALU for one iteration.
 //
 // traverse (longSA.cpp:297-316) over an interval [start, end] whose suffixes
@@ -731,7 +738,9 @@ __global__ __launch_bounds__(BLOCK, GEO ? SM_GEO_WPS : 1) void k_mam_sm(const Ct
   uint32_t fl = 0;
   FlagRef need2{fl, 0};
   uint64_t rd = 0;
-  uint32_t L = 0, nem = 0;
+  // (GEO: every read has GEO bases; starting from that, and not from 0, L is
+  // the constant in every use and holds no register)
+  uint32_t L = GEO ? uint32_t(GEO) : 0u, nem = 0;
   Bad bad{0, 0, 0, 0, 0, 0, 0, 0};
   // search state (longSA.h interval_t + prefix)
   uint32_t prefix = 0, depth = 0;
@@ -783,16 +792,20 @@ __global__ __launch_bounds__(BLOCK, GEO ? SM_GEO_WPS : 1) void k_mam_sm(const Ct
   // probe m decided: P' agrees with S_m on lc characters past cbase; ranout:
   // P' ran out (it is a prefix of S_m), else its next byte pb differs from
   // the text's tb (signed chars, like the reference)
-  auto bs_decide = [&](bool ranout, uint32_t pb, uint32_t tb) {
+  // (on: the probe is decided -- false leaves everything as it is; the updates
+  // are selects, so a caller's "decided?" needs no block of its own)
+  auto bs_decide = [&](bool on, bool ranout, uint32_t pb, uint32_t tb) {
     bool left;                                  // keep [lo, m) (else (m, hi))
     if (bsm == BS_INSERT) {
       left = ranout || int8_t(pb) < int8_t(tb);
-      if (lc > best) { best = lc; bpos = sp; bi = m; }
+      const bool up = on && lc > best;
+      best = up ? lc : best; bpos = up ? sp : bpos; bi = up ? m : bi;
     } else {                                    // in the run iff lcp reaches cap
       left = (lc >= cap) == (bsm == BS_LEFT);
     }
-    if (left) { hi = m; lR = lc; }
-    else { lo = m + 1; lL = lc; }
+    const bool l = on && left, r = on && !left;
+    hi = l ? m : hi; lR = l ? lc : lR;
+    lo = r ? m + 1 : lo; lL = r ? lc : lL;
   };
   // compare P' with T[sp + cbase + lc ...] (sp = the SA word of probe m).
   // Packed words: the 7 bases T[x + K ...) in the word decide a compare that
@@ -802,27 +815,30 @@ __global__ __launch_bounds__(BLOCK, GEO ? SM_GEO_WPS : 1) void k_mam_sm(const Ct
   auto bs_probe = [&]() -> bool {
     SM_HOOK_CMPBS(true, sp, cbase + lc);
     const uint32_t o = cbase + lc;
+    bool dec = false;
     if (PK && ((sp >> kPkPosBits) & 7u) != 5u && o - gK < kPkWindow) {
       const uint32_t rem = cap - lc, nav = gK + kPkWindow - o;
       const uint32_t lim = rem < nav ? rem : nav;
       const uint64_t win = pk_window(sp) >> (8 * (o - gK));
       const uint32_t k = agree8(win, lds_load8(P, prefix + o), lim);
       lc += k;
-      if (k < lim || k == rem) {
-        SM_HOOK_CMPBS(false, sp, cbase + lc);
-        bs_decide(k == rem, k == rem ? 0u : uint32_t(P[prefix + o + k]),
-                  uint32_t(win >> (8 * (k & 7))) & 0xFFu);
-        pf = false; pfr = false; need2 = false;
-        return true;
-      }
+      dec = k < lim || k == rem;
+      if (dec) { SM_HOOK_CMPBS(false, sp, cbase + lc); }
+      // (the read byte past a read that ran out is not used: offset 0 then)
+      bs_decide(dec, k == rem, uint32_t(P[k == rem ? 0u : prefix + o + k]),
+                uint32_t(win >> (8 * (k & 7))) & 0xFFu);
     }
-    addr = reinterpret_cast<uint64_t>(c.T + (sp & PM) + cbase + lc);
-    addr2 = ia(c.SA, (lo + m) >> 1);
-    need2 = SM_KNOB(pf, 1u) && lo < m;
-    pfr = SM_KNOB(pf, 1u) && m + 1 < hi;
-    pf = SM_KNOB(pf, 1u) != 0;
-    st = S_CMP; op = O_BS;
-    return false;
+    if (dec) {
+      pf = false; pfr = false; need2 = false;
+    } else {
+      addr = reinterpret_cast<uint64_t>(c.T + (sp & PM) + cbase + lc);
+      addr2 = ia(c.SA, (lo + m) >> 1);
+      need2 = SM_KNOB(pf, 1u) && lo < m;
+      pfr = SM_KNOB(pf, 1u) && m + 1 < hi;
+      pf = SM_KNOB(pf, 1u) != 0;
+      st = S_CMP; op = O_BS;
+    }
+    return dec;
   };
   auto lblock = [&](uint64_t e) { return reinterpret_cast<uint64_t>(c.L8 + (e >= 15 ? e - 15 : 0)); };
   // (ls / rs: that side's end is known already, from packed-word L8 bytes)
@@ -965,6 +981,13 @@ __global__ __launch_bounds__(BLOCK, GEO ? SM_GEO_WPS : 1) void k_mam_sm(const Ct
           need2 = !gDirect && c.c_bad > 1;
           pf = false; pfr = false;
           bad = Bad{0, 0, 0, 0, 0, 0, 0, 0};
+          // the new read's search state, reset here and not in S_COPY's consume
+          // block: this if-block overwrites the registers in place, while
+          // constants assigned in one consume block among nine reached the
+          // blocks' merge through temporaries and a copy back per value
+          prefix = 0; depth = 0; start = 0; end = N - 1; have_pos = false; nem = 0;
+          skip_f = false; fm = 0; ktr_set = false;
+          fk = 0; kp = 0; kx = 0xFFFFFFFFu; fdead = false;
           st = S_COPY;
         }
       }
@@ -1013,59 +1036,54 @@ __global__ __launch_bounds__(BLOCK, GEO ? SM_GEO_WPS : 1) void k_mam_sm(const Ct
     }
 
     // ---------------- consume ----------------
-    switch (st) {
-      case S_ALU:
-        SM_REGION(1);
-        a = pend;
-        break;
-      case S_COPY: {                                 // bad-mask chunks 0 (v), 1 (v2)
-        SM_REGION(2);
-        if (!gDirect) {   // (direct rows: the wave set the mask above)
-          bad.w0 = v.x; bad.w1 = v.y; bad.w2 = v.z; bad.w3 = v.w;
-          bad.w4 = v2.x; bad.w5 = v2.y; bad.w6 = v2.z; bad.w7 = v2.w;   // (zero: c_bad 1)
-        }
-        need2 = false;
-        prefix = 0; depth = 0; start = 0; end = N - 1; have_pos = false; nem = 0;
-        skip_f = false; fm = 0; ktr_set = false;
-        fk = 0; kp = 0; kx = 0xFFFFFFFFu; fdead = false;
-        clean = (bad.w0 | bad.w1 | bad.w2 | bad.w3 | bad.w4 | bad.w5 | bad.w6 | bad.w7) == 0;
-        a = A_TOP;
-        break;
+    const uint32_t st0 = st;   // (the bodies below change st; each runs for the state that arrived)
+    if (st0 == S_ALU) {
+      SM_REGION(1);
+      a = pend;
+    }
+    if (st0 == S_COPY) {                                 // bad-mask chunks 0 (v), 1 (v2)
+      SM_REGION(2);
+      if (!gDirect) {   // (direct rows: the wave set the mask above)
+        bad.w0 = v.x; bad.w1 = v.y; bad.w2 = v.z; bad.w3 = v.w;
+        bad.w4 = v2.x; bad.w5 = v2.y; bad.w6 = v2.z; bad.w7 = v2.w;   // (zero: c_bad 1)
       }
-      case S_BM: {                                   // (F) a k-mer table entry arrived
-        SM_REGION(3);
-        const bool two = need2;   // (policy 3: v2 holds the entry 3 bases on)
-        need2 = false;
-        if (SM_KNOB(bm_dual, 3u) == 3) {
-          // the entry of the k-mer at x = kp + fj + 2; c0 = the 2-bit codes of
-          // the k + 4 read bases [x - 2, x + k + 2), first most significant:
-          // its presence bits give the B-mers at x - 2, x - 1, x (common.hpp).
-          // two: v2 / c1 are the same for the k-mer at x + 3
-          const uint32_t nb = 2 * (gK + 4);
-          auto entry_bits = [&](const uint4 &e, uint64_t cc) {
-            const uint64_t f48 = kt_filter(lo64(e), hi64(e));
-            const uint32_t l1 = uint32_t(cc >> (nb - 2)) & 3, l0 = uint32_t(cc >> (nb - 4)) & 3;
-            const uint32_t r1 = uint32_t(cc >> 2) & 3, r2 = uint32_t(cc) & 3;
-            return (uint32_t(f48 >> (32 + 4 * l1 + l0)) & 1u) |
-                   ((uint32_t(f48 >> (16 + 4 * l0 + r1)) & 1u) << 1) |
-                   ((uint32_t(f48 >> (4 * r1 + r2)) & 1u) << 2);
-          };
-          const uint32_t bits = entry_bits(v, c0);
-          SM_HOOK_F(fj, bits);
-          fk |= (7u << fj) | (bits << (16 + fj));
-          fdead = bits != 7u;
-          if (two) {
-            const uint32_t bits2 = entry_bits(v2, c1);
-            SM_HOOK_F(fj + 3, bits2);
-            fk |= (7u << (fj + 3)) | (bits2 << (19 + fj));
-            fdead = fdead || bits2 != 7u;
-          }
-          kx = kp + fj + 2;
-          klo = lo64(v) & kKtMask;
-          khi = hi64(v) & kKtMask;
-          a = A_TOP;
-          break;
+      need2 = false;   // (the search state was reset where the read was assigned)
+      clean = (bad.w0 | bad.w1 | bad.w2 | bad.w3 | bad.w4 | bad.w5 | bad.w6 | bad.w7) == 0;
+      a = A_TOP;
+    }
+    if (st0 == S_BM) {                                   // (F) a k-mer table entry arrived
+      SM_REGION(3);
+      const bool two = need2;   // (policy 3: v2 holds the entry 3 bases on)
+      need2 = false;
+      if (SM_KNOB(bm_dual, 3u) == 3) {
+        // the entry of the k-mer at x = kp + fj + 2; c0 = the 2-bit codes of
+        // the k + 4 read bases [x - 2, x + k + 2), first most significant:
+        // its presence bits give the B-mers at x - 2, x - 1, x (common.hpp).
+        // two: v2 / c1 are the same for the k-mer at x + 3
+        const uint32_t nb = 2 * (gK + 4);
+        auto entry_bits = [&](const uint4 &e, uint64_t cc) {
+          const uint64_t f48 = kt_filter(lo64(e), hi64(e));
+          const uint32_t l1 = uint32_t(cc >> (nb - 2)) & 3, l0 = uint32_t(cc >> (nb - 4)) & 3;
+          const uint32_t r1 = uint32_t(cc >> 2) & 3, r2 = uint32_t(cc) & 3;
+          return (uint32_t(f48 >> (32 + 4 * l1 + l0)) & 1u) |
+                 ((uint32_t(f48 >> (16 + 4 * l0 + r1)) & 1u) << 1) |
+                 ((uint32_t(f48 >> (4 * r1 + r2)) & 1u) << 2);
+        };
+        const uint32_t bits = entry_bits(v, c0);
+        SM_HOOK_F(fj, bits);
+        fk |= (7u << fj) | (bits << (16 + fj));
+        fdead = bits != 7u;
+        if (two) {
+          const uint32_t bits2 = entry_bits(v2, c1);
+          SM_HOOK_F(fj + 3, bits2);
+          fk |= (7u << (fj + 3)) | (bits2 << (19 + fj));
+          fdead = fdead || bits2 != 7u;
         }
+        kx = kp + fj + 2;
+        klo = lo64(v) & kKtMask;
+        khi = hi64(v) & kKtMask;
+        a = A_TOP;
+      } else {
         // The last B-mer [q1, q1+B) (q1 = prefix+min_len-B) is probed first:
         // absent, it lies inside every window starting in [prefix, q1], so
         // all of them are skipped at once; an absent first B-mer rules out
@@ -1120,171 +1138,166 @@ __global__ __launch_bounds__(BLOCK, GEO ? SM_GEO_WPS : 1) void k_mam_sm(const Ct
           skip_f = true;                              // window passed: go on at (C)
           a = A_TOP;
         }
-        break;
       }
-      case S_KT: {                                   // (C)
-        SM_REGION(4);
-        const uint64_t l0 = lo64(v) & kKtMask, h0 = hi64(v) & kKtMask;
-        if (l0 <= h0) { depth = gK; start = l0; end = h0; have_pos = false; }
-        a = A_TRAV;
-        break;
+    }
+    if (st0 == S_KT) {                                   // (C)
+      SM_REGION(4);
+      const uint64_t l0 = lo64(v) & kKtMask, h0 = hi64(v) & kKtMask;
+      if (l0 <= h0) { depth = gK; start = l0; end = h0; have_pos = false; }
+      a = A_TRAV;
+    }
+    if (st0 == S_IDX) {
+      SM_REGION(5);
+      const uint64_t iv = idx_val<IdxT>(v, ao);
+      const uint64_t iv2 = idx_val<IdxT>(v2, uint32_t(addr2) & 15);
+      // (PK: the ISA words of an expand_link's ends -- one word for a
+      // suffix link's target (O_ISAJ), two for a non-singleton's; one site)
+      if (PK && (op == O_ISAJ || op == O_NS_ISA2)) isa_hints(iv, op == O_ISAJ ? iv : iv2);
+      // one straight body of selects over the op (each op's own block
+      // merged its few assignments through copies of everything the others
+      // touch: addr, addr2, op, sp, the flags)
+      const uint32_t op0 = op;
+      const bool sap = op0 <= O_SAPOS2, bsa = op0 == O_BS_SA, isj = op0 == O_ISAJ;
+      const bool ns1 = op0 == O_NS_SA2, ns2 = op0 == O_NS_ISA2, se = isj || ns2;
+      const uint64_t p1 = iv & PM, p2 = iv2 & PM;
+      pos = sap ? iv : pos;
+      sp = bsa ? iv : sp;                           // probe m: compare from lcp lc
+      start = se ? p1 : start;
+      end = isj ? p1 : ns2 ? p2 : end;
+      fl = sap ? fl | 2u : se ? fl & ~(2u | uint32_t(ns2)) : fl;   // have_pos; need2 off after O_NS_ISA2
+      addr = ns1 ? ia(c.ISA, p1 + 1) : addr;        // suffix link, both ends
+      addr2 = ns1 ? ia(c.ISA, p2 + 1) : addr2;
+      op = ns1 ? uint32_t(O_NS_ISA2) : op0;
+      prefix += uint32_t(ns2);
+      // O_SAPOS -> A_TRAV, O_SAPOS2 -> A_AFTER, O_BS_SA -> A_BSP (16 bytes
+      // first: a binary-search probe usually decides early), O_ISAJ ->
+      // A_EXPAND, O_NS_SA2 -> the ISA probes, O_NS_ISA2 -> A_EXPAND or the root
+      constexpr uint32_t nxt = A_TRAV | (A_AFTER << 4) | (A_BSP << 8) | (A_EXPAND << 12) |
+                               (A_NONE << 16) | (A_EXPAND << 20);
+      a = (nxt >> (4 * op0)) & 15u;
+      a = ns2 && depth == 0 ? uint32_t(A_TOPR) : a;
+    }
+    if (st0 == S_BYTE) {                                 // is_leftmaximal: T[pos-1]
+      SM_REGION(6);
+      SM_HOOK_BYTE(pos & PM);
+      em = P[prefix - 1] != uint8_t(byte_at(v, ao));
+      a = A_EMIT;
+    }
+    if (st0 == S_CMP) {                                  // (A) extension / traverse probe
+      SM_REGION(7);
+      // text bytes [addr, addr + 16) in v, then (tn2) the next 16 in v2
+      // (pf: v2 / v3 hold the children's SA elements instead)
+      const bool tn2 = need2 && !pf;
+      const uint32_t off = prefix + (op == O_BS ? cbase : depth) + lc;
+      const uint32_t rem = op == O_BS ? cap - lc : L - off;
+      const uint32_t lim = rem < 16 ? rem : 16u;
+      uint32_t k = agree_block(v, 0, P, off, lim);
+      if (tn2 && k == lim && k < rem) {
+        const uint32_t lim2 = rem - k < 16 ? rem - k : 16u;
+        k += agree_block(v2, 0, P, off + k, lim2);
       }
-      case S_IDX: {
-        SM_REGION(5);
-        const uint64_t iv = idx_val<IdxT>(v, ao);
-        const uint64_t iv2 = idx_val<IdxT>(v2, uint32_t(addr2) & 15);
-        // (PK: the ISA words of an expand_link's ends -- one word for a
-        // suffix link's target (O_ISAJ), two for a non-singleton's; one site)
-        if (PK && (op == O_ISAJ || op == O_NS_ISA2)) isa_hints(iv, op == O_ISAJ ? iv : iv2);
-        if (op == O_SAPOS || op == O_SAPOS2) {
-          pos = iv; have_pos = true;
-          a = op == O_SAPOS ? A_TRAV : A_AFTER;
-        } else if (op == O_BS_SA) {                   // probe m: compare from lcp lc
-          sp = iv;
-          // 16 bytes first: a binary-search probe usually decides early
-          a = A_BSP;
-        } else if (op == O_ISAJ) {
-          start = end = iv & PM; have_pos = false;
-          a = A_EXPAND;
-        } else if (op == O_NS_SA2) {                  // suffix link, both ends
-          addr = ia(c.ISA, (iv & PM) + 1); addr2 = ia(c.ISA, (iv2 & PM) + 1);
-          op = O_NS_ISA2;
-        } else {                                      // O_NS_ISA2
-          start = iv & PM; end = iv2 & PM; need2 = false;
-          ++prefix; have_pos = false;
-          if (depth == 0) { start = 0; end = N - 1; a = A_TOP; }
-          else a = A_EXPAND;
-        }
-        break;
-      }
-      case S_BYTE: {                                 // is_leftmaximal: T[pos-1]
-        SM_REGION(6);
-        SM_HOOK_BYTE(pos & PM);
-        em = P[prefix - 1] != uint8_t(byte_at(v, ao));
-        a = A_EMIT;
-        break;
-      }
-      case S_CMP: {                                  // (A) extension / traverse probe
-        SM_REGION(7);
-        // text bytes [addr, addr + 16) in v, then (tn2) the next 16 in v2
-        // (pf: v2 / v3 hold the children's SA elements instead)
-        const bool tn2 = need2 && !pf;
-        const uint32_t off = prefix + (op == O_BS ? cbase : depth) + lc;
-        const uint32_t rem = op == O_BS ? cap - lc : L - off;
-        const uint32_t lim = rem < 16 ? rem : 16u;
-        uint32_t k = agree_block(v, 0, P, off, lim);
-        if (tn2 && k == lim && k < rem) {
-          const uint32_t lim2 = rem - k < 16 ? rem - k : 16u;
-          k += agree_block(v2, 0, P, off + k, lim2);
-        }
-        const uint32_t got = tn2 ? (rem < 32 ? rem : 32u) : lim;   // bytes available
-        const bool had_pf = pf;
-        pf = false; pfr = false;
-        lc += k;
-        if (k == got && k < rem) {                    // agreed on all loaded bytes: go on
-          addr += k;
-          addr2 = addr + 16;
-          need2 = rem - k > 16;
-        } else if (op == O_EXT) {
-          need2 = false;
-          depth += lc; lc = 0;
-          a = A_AFTER;
-        } else {                                      // O_BS: probe m decided
-          SM_HOOK_CMPBS(false, sp, cbase + lc);
-          need2 = false;
-          // P' < S_m iff P' ran out (prefix of S_m) or the first differing
-          // byte of P' is smaller
-          const uint32_t tbyte = k < 16 ? byte_at(v, k) : byte_at(v2, k - 16);
-          bs_decide(k == rem, k == rem ? 0u : uint32_t(P[off + k]), tbyte);
-          const bool left = hi == m;
-          if (had_pf && lo < hi) {                    // the next probe's SA element is here
-            m = (lo + hi) >> 1;
-            SM_HOOK_PF(ia(c.SA, m));
-            sp = left ? idx_val<IdxT>(v2, uint32_t(m * sizeof(IdxT)) & 15) : v3;
-            lc = lL < lR ? lL : lR;
-            a = A_BSP;
-          } else {
-            a = A_BS;
-          }
-        }
-        break;
-      }
-      case S_USCAN: {                                // (B) first j with U[pos+j] >= d-j
-        SM_REGION(8);
-        // U bytes [addr, addr + 16) in v, then (need2) the next 16 in v2
-        bool fin = false;
-#pragma unroll
-        for (uint32_t h = 0; h < 2; ++h) {
-          if (fin || (h == 1 && !need2)) break;
-          const uint32_t D = dch - j;
-          const uint32_t lim = D < 16 ? D : 16u;
-          const uint32_t inr = (1u << lim) - 1;
-          const uint32_t hm = (h ? mv2 : mv) & inr;   // U[.+i] + i >= D
-          if (hm) {
-            j += uint32_t(__builtin_ctz(hm)); hit = true; fin = true;
-          } else {
-            j += lim;
-            if (j >= dch) { hit = false; fin = true; }
-          }
-        }
-        if (fin) {
-          need2 = false;
-          a = A_CHAIN_DONE;
-        } else {
-          addr += need2 ? 32 : 16;
-          addr2 = addr + 16;
-          need2 = SM_KNOB(u32, 1u) && dch - j > 16;
-        }
-        break;
-      }
-      case S_EXL:                                    // L8 runs: expand_link (xrun = 0)
-      case S_EXR:                                    // or the traverse's final run (1);
-      case S_EXB: {                                  // S_EXB: both sides in one iteration
-        SM_REGION(9);
-        const uint64_t lb = xrun ? start : 0, hb = xrun ? end : N - 1;
-        // run members before the stop in one block, walking down (left:
-        // bytes (o-lim, o]) or up (right: bytes [o, o+lim)); *more: no stop
-        // in the window and room beyond it
-        auto side = [&](uint32_t mask, uint32_t o, bool left, bool &more) {
-          const uint64_t room = left ? es - lb : hb - ee;
-          const uint32_t w = left ? o + 1 : 16 - o;
-          const uint32_t lim = room < uint64_t(w) ? uint32_t(room) : w;
-          const uint32_t below = ~mask & 0xFFFFu;      // L8 < xd
-          const uint32_t win = left ? (((1u << lim) - 1) << (o + 1 - lim)) : (((1u << lim) - 1) << o);
-          const uint32_t sm = below & win;
-          const uint32_t k = sm ? (left ? o - (31 - __builtin_clz(sm)) : uint32_t(__builtin_ctz(sm)) - o)
-                                : lim;
-          more = !sm && uint64_t(k) < room;
-          return k;
-        };
-        bool moreL = false, moreR = false;
-        // the left block ends at es (position es - its start), the right one
-        // starts at ee + 1 (position 0)
-        if (st != S_EXR)
-          es -= side(mv, uint32_t(es - (addr - reinterpret_cast<uint64_t>(c.L8))), true, moreL);
-        if (st != S_EXL) {
-          const bool b2 = st == S_EXB;
-          ee += side(b2 ? mv2 : mv, 0u, false, moreR);
-          if (b2) rdone = !moreR;
-        }
+      const uint32_t got = tn2 ? (rem < 32 ? rem : 32u) : lim;   // bytes available
+      const bool had_pf = pf;
+      pf = false; pfr = false;
+      lc += k;
+      if (k == got && k < rem) {                    // agreed on all loaded bytes: go on
+        addr += k;
+        addr2 = addr + 16;
+        need2 = rem - k > 16;
+      } else if (op == O_EXT) {
         need2 = false;
-        const bool left = st != S_EXR;                // the side that continues here
-        const bool more = left ? moreL : moreR;
-        if (!more) {
-          a = left ? A_XL_DONE : A_RUN_DONE;
-        } else if (++nblk < SM_KNOB(lin_blocks, 8u)) {
-          addr = left ? lblock(es) : reinterpret_cast<uint64_t>(c.L8 + ee + 1);
-          st = left ? S_EXL : S_EXR;
-        } else {                                      // long run: bisect for its end
-          bsm = left ? BS_LEFT : BS_RIGHT;
-          if (left) { lo = lb; hi = es; lL = 0; lR = cap; }
-          else { lo = ee + 1; hi = hb + 1; lL = cap; lR = 0; }
+        depth += lc; lc = 0;
+        a = A_AFTER;
+      } else {                                      // O_BS: probe m decided
+        SM_HOOK_CMPBS(false, sp, cbase + lc);
+        need2 = false;
+        // P' < S_m iff P' ran out (prefix of S_m) or the first differing
+        // byte of P' is smaller
+        const uint32_t tbyte = k < 16 ? byte_at(v, k) : byte_at(v2, k - 16);
+        bs_decide(true, k == rem, k == rem ? 0u : uint32_t(P[off + k]), tbyte);
+        const bool left = hi == m;
+        if (had_pf && lo < hi) {                    // the next probe's SA element is here
+          m = (lo + hi) >> 1;
+          SM_HOOK_PF(ia(c.SA, m));
+          sp = left ? idx_val<IdxT>(v2, uint32_t(m * sizeof(IdxT)) & 15) : v3;
+          lc = lL < lR ? lL : lR;
+          a = A_BSP;
+        } else {
           a = A_BS;
         }
-        break;
       }
-      default:
-        break;
+    }
+    if (st0 == S_USCAN) {                                // (B) first j with U[pos+j] >= d-j
+      SM_REGION(8);
+      // U bytes [addr, addr + 16) in v, then (need2) the next 16 in v2
+      bool fin = false;
+#pragma unroll
+      for (uint32_t h = 0; h < 2; ++h) {
+        if (fin || (h == 1 && !need2)) break;
+        const uint32_t D = dch - j;
+        const uint32_t lim = D < 16 ? D : 16u;
+        const uint32_t inr = (1u << lim) - 1;
+        const uint32_t hm = (h ? mv2 : mv) & inr;   // U[.+i] + i >= D
+        if (hm) {
+          j += uint32_t(__builtin_ctz(hm)); hit = true; fin = true;
+        } else {
+          j += lim;
+          if (j >= dch) { hit = false; fin = true; }
+        }
+      }
+      if (fin) {
+        need2 = false;
+        a = A_CHAIN_DONE;
+      } else {
+        addr += need2 ? 32 : 16;
+        addr2 = addr + 16;
+        need2 = SM_KNOB(u32, 1u) && dch - j > 16;
+      }
+    }
+    // L8 runs: expand_link (xrun = 0) or the traverse's final run (1);
+    // S_EXB: both sides in one iteration
+    if (st0 >= S_EXL) {   // S_EXL, S_EXR, S_EXB
+      SM_REGION(9);
+      const uint64_t lb = xrun ? start : 0, hb = xrun ? end : N - 1;
+      // run members before the stop in one block, walking down (left:
+      // bytes (o-lim, o]) or up (right: bytes [o, o+lim)); *more: no stop
+      // in the window and room beyond it
+      auto side = [&](uint32_t mask, uint32_t o, bool left, bool &more) {
+        const uint64_t room = left ? es - lb : hb - ee;
+        const uint32_t w = left ? o + 1 : 16 - o;
+        const uint32_t lim = room < uint64_t(w) ? uint32_t(room) : w;
+        const uint32_t below = ~mask & 0xFFFFu;      // L8 < xd
+        const uint32_t win = left ? (((1u << lim) - 1) << (o + 1 - lim)) : (((1u << lim) - 1) << o);
+        const uint32_t sm = below & win;
+        const uint32_t k = sm ? (left ? o - (31 - __builtin_clz(sm)) : uint32_t(__builtin_ctz(sm)) - o)
+                              : lim;
+        more = !sm && uint64_t(k) < room;
+        return k;
+      };
+      bool moreL = false, moreR = false;
+      // the left block ends at es (position es - its start), the right one
+      // starts at ee + 1 (position 0)
+      if (st != S_EXR)
+        es -= side(mv, uint32_t(es - (addr - reinterpret_cast<uint64_t>(c.L8))), true, moreL);
+      if (st != S_EXL) {
+        const bool b2 = st == S_EXB;
+        ee += side(b2 ? mv2 : mv, 0u, false, moreR);
+        if (b2) rdone = !moreR;
+      }
+      need2 = false;
+      const bool left = st != S_EXR;                // the side that continues here
+      const bool more = left ? moreL : moreR;
+      if (!more) {
+        a = left ? A_XL_DONE : A_RUN_DONE;
+      } else if (++nblk < SM_KNOB(lin_blocks, 8u)) {
+        addr = left ? lblock(es) : reinterpret_cast<uint64_t>(c.L8 + ee + 1);
+        st = left ? S_EXL : S_EXR;
+      } else {                                      // long run: bisect for its end
+        bsm = left ? BS_LEFT : BS_RIGHT;
+        if (left) { lo = lb; hi = es; lL = 0; lR = cap; }
+        else { lo = ee + 1; hi = hb + 1; lL = cap; lR = 0; }
+        a = A_BS;
+      }
     }
 
     if (gPad) {                                    // issue-bound experiment (SMASH_SM_PAD)
@@ -1299,6 +1312,7 @@ __global__ __launch_bounds__(BLOCK, GEO ? SM_GEO_WPS : 1) void k_mam_sm(const Ct
 
     // ---------------- decide ----------------
     if (a == A_BSP) {                                 // probe m's SA word is in sp
+      SM_REGION(28);
       a = bs_probe() ? A_BS : A_NONE;
     }
     if (a == A_BS) {                                  // next probe of a binary search
@@ -1316,18 +1330,16 @@ __global__ __launch_bounds__(BLOCK, GEO ? SM_GEO_WPS : 1) void k_mam_sm(const Ct
     if (a == A_BS_DONE) {
       SM_REGION(11);
       lc = 0;
-      if (bsm == BS_LEFT) {
-        es = lo;                                      // first suffix of the run
-        a = A_XL_DONE;
-      } else if (bsm == BS_RIGHT) {
-        ee = lo - 1;                                  // last suffix of the run
-        a = A_RUN_DONE;
-      } else if (best == 0) {
-        a = A_AFTER;                                  // no longer match: interval unchanged
-      } else {                                        // the run of suffixes sharing best more
+      // a run's end found (BS_LEFT: its first suffix, BS_RIGHT: its last), or
+      // the traverse's search: no longer match (interval unchanged), else the
+      // run of suffixes sharing best more around bi.  The ends as selects
+      const bool bl = bsm == BS_LEFT, br = bsm == BS_RIGHT, run = bsm == BS_INSERT && best != 0;
+      es = bl ? lo : run ? bi : es;
+      ee = br ? lo - 1 : run ? bi : ee;
+      a = bl ? uint32_t(A_XL_DONE) : br ? uint32_t(A_RUN_DONE) : uint32_t(A_AFTER);
+      if (run) {
         xd = depth + best; xrun = true;
         cbase = depth; cap = best;
-        es = bi; ee = bi;
         SM_HOOK_RUN(true, 1, 0, 0);
         // packed: the SA word of rank bi holds L8[bi] and L8[bi + 1], the
         // run's first stop on either side when it ends at bi
@@ -1354,6 +1366,7 @@ __global__ __launch_bounds__(BLOCK, GEO ? SM_GEO_WPS : 1) void k_mam_sm(const Ct
       a = A_EXS;
     }
     if (a == A_EXS) {                                 // (one site: the two runs above)
+      SM_REGION(29);
       a = ex_start(xrun ? start : 0, xrun ? end : N - 1, xls, xrs) ? A_NONE : A_RUN_DONE;
     }
     if (a == A_XL_DONE) {                             // left end known: right side
@@ -1362,8 +1375,7 @@ __global__ __launch_bounds__(BLOCK, GEO ? SM_GEO_WPS : 1) void k_mam_sm(const Ct
       nblk = 0;
       if (!xrun && start - es >= thresh) {            // expand_link gives up (longSA.h:164)
         SM_HOOK_RUN(false, 0, start - es, 99);
-        depth = 0; start = 0; end = N - 1; have_pos = false;
-        a = A_TOP;
+        a = A_TOPR;
       } else if (ee < hb && !rdone) {
         addr = reinterpret_cast<uint64_t>(c.L8 + ee + 1);
         st = S_EXR;
@@ -1378,20 +1390,16 @@ __global__ __launch_bounds__(BLOCK, GEO ? SM_GEO_WPS : 1) void k_mam_sm(const Ct
       if (xrun) {                                     // traverse result
         start = es; end = ee; depth = xd; pos = bpos; have_pos = start == end;
         a = A_AFTER;
-      } else if ((start - es) + (ee - end) >= thresh) {
-        depth = 0; start = 0; end = N - 1; have_pos = false;
-        a = A_TOP;
-      } else {                                        // expand_link succeeded
+      } else {                                        // expand_link succeeded, or gave up
+        a = (start - es) + (ee - end) >= thresh ? A_TOPR : A_TOP;
         start = es; end = ee;
-        a = A_TOP;
       }
     }
     if (a == A_CHAIN_DONE) {
       SM_REGION(14);
       prefix += j;
       if (!hit) {
-        depth = 0; start = 0; end = N - 1; have_pos = false;
-        a = A_TOP;
+        a = A_TOPR;
       } else {
         depth = dch - j;
         addr = ia(c.ISA, (pos & PM) + j);
@@ -1399,8 +1407,13 @@ __global__ __launch_bounds__(BLOCK, GEO ? SM_GEO_WPS : 1) void k_mam_sm(const Ct
         a = A_NONE;
       }
     }
-    if (a == A_TOP) {
+    if (a == A_TOP || a == A_TOPR) {
       SM_REGION(17);
+      if (a != A_TOP) {                               // A_TOPR: back to the root
+        SM_REGION(31);
+        depth = 0; start = 0; end = N - 1; have_pos = false;
+        a = A_TOP;
+      }
       uint32_t kpos = ~0u;                            // a k-mer table probe's read window
       // the read's bad bits [prefix, prefix + 64) as this A_TOP starts: the
       // window tests below are shifts of them (prefix only grows here, by at
@@ -1585,9 +1598,17 @@ __global__ __launch_bounds__(BLOCK, GEO ? SM_GEO_WPS : 1) void k_mam_sm(const Ct
     if (a == A_TRAV) {
       SM_REGION(18);
       if (depth >= L || prefix + depth >= L) {
-        a = A_AFTER;                                  // (backwards: parks in S_ALU)
+        a = A_AFTER;
       } else {
         a = A_NONE;
+        // the binary search's registers are set for the singleton too (it
+        // reads none of them before a later search sets them again): assigned
+        // on one arm only, each constant reaches the merge through a
+        // temporary and a copy back
+        lo = start; hi = end + 1; lL = 0; lR = 0; best = 0;
+        bsm = BS_INSERT; cbase = depth; cap = L - prefix - depth;
+        m = (lo + hi) >> 1;
+        lc = 0;
         if (start == end) {                          // (A) singleton: extend
           if (!have_pos) {
             addr = ia(c.SA, start);
@@ -1596,14 +1617,10 @@ __global__ __launch_bounds__(BLOCK, GEO ? SM_GEO_WPS : 1) void k_mam_sm(const Ct
             addr = reinterpret_cast<uint64_t>(c.T + (pos & PM) + depth);
             addr2 = addr + 16;
             need2 = L - prefix - depth > 16;
-            st = S_CMP; op = O_EXT; lc = 0;
+            st = S_CMP; op = O_EXT;
           }
         } else {                                     // search [start, end] for P'
           SM_HOOK_BS(end - start + 1, depth);
-          lo = start; hi = end + 1; lL = 0; lR = 0; best = 0;
-          bsm = BS_INSERT; cbase = depth; cap = L - prefix - depth;
-          m = (lo + hi) >> 1;
-          lc = 0;
           addr = ia(c.SA, m);
           st = S_IDX; op = O_BS_SA;
         }
@@ -1612,8 +1629,8 @@ __global__ __launch_bounds__(BLOCK, GEO ? SM_GEO_WPS : 1) void k_mam_sm(const Ct
     if (a == A_AFTER) {
       SM_REGION(16);
       if (depth <= 1) {
-        depth = 0; start = 0; end = N - 1; have_pos = false; ++prefix;
-        a = A_TOP;
+        ++prefix;
+        a = A_TOPR;                                   // (backwards: parks in S_ALU)
       } else {
         a = A_NONE;
         if (start != end) {                          // non-singleton suffix link
@@ -1637,6 +1654,7 @@ __global__ __launch_bounds__(BLOCK, GEO ? SM_GEO_WPS : 1) void k_mam_sm(const Ct
       }
     }
     if (a == A_EMIT) {                                // (one site: S_BYTE and A_AFTER)
+      SM_REGION(30);
       if (em) {
         if (nem < gCap)
           c.out[rd * gCap + nem] =

@@ -9,7 +9,7 @@ from collections import Counter
 src = open(sys.argv[2]).read().split("\n")
 marks = []
 for i, l in enumerate(src, 1):
-    m = re.search(r"case (S_[A-Z]+)|if \(a == (A_[A-Z_]+)\)|(// ---------------- decide)|(for \(;;\) \{)", l)
+    m = re.search(r"case (S_[A-Z]+)|if \(st0 [=>]= (S_[A-Z]+)\)|if \(a == (A_[A-Z_]+)[ )]|(// ---------------- decide)|(for \(;;\) \{)", l)
     if m:
         marks.append((i, next(g for g in m.groups() if g)))
 body0 = next(i for i, n in marks if n.startswith("for"))

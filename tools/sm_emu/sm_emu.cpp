@@ -196,8 +196,36 @@ static void emu_hook_byte(uint64_t pos) {
 #define SM_HOOK_CMPBS(begin, sp, off) emu_hook_cmpbs(begin, sp, off)
 #define SM_HOOK_RUN(begin, kind, el, er) emu_hook_run(begin, kind, el, er)
 #define SM_HOOK_BYTE(pos) emu_hook_byte(pos)
+// path coverage (tests/test_sm_emu_paths.py): the blocks the lane enters
+// (SM_REGION numbers; 0 opens an iteration's consume) and, among the consume
+// and decide blocks (1-19, 28-30), which block follows which within one
+// iteration: [33 * from + to], to = 0: the iteration ended there (a probe was
+// named, or the read finished), 32: the chain parked in S_ALU; [33 * from +
+// 31]: the block that sent the lane to A_TOP through the root reset
+static uint64_t emu_region_n[32], emu_edge[33 * 33];
+static int emu_prev = 0, emu_prev2 = 0;
+static void emu_region(int k) {
+  ++emu_region_n[k];
+  if (k == 0) {
+    if (emu_prev) ++emu_edge[33 * emu_prev];
+    emu_prev = emu_prev2 = 0;
+  } else if (k == 31) {   // (entered inside A_TOP, 17: that edge is this one)
+    --emu_edge[33 * emu_prev2 + 17];
+    ++emu_edge[33 * emu_prev2 + 31];
+  } else if (k < 20 || (k >= 28 && k <= 30)) {
+    ++emu_edge[33 * emu_prev + k];
+    emu_prev2 = emu_prev;
+    emu_prev = k;
+  }
+}
+#define SM_REGION(k) emu_region(k)
 static uint64_t emu_park[16];
-#define SM_HOOK_PARK(a) (++emu_park[(a) & 15])
+static void emu_hook_park(uint32_t a) {
+  ++emu_park[a & 15];
+  ++emu_edge[33 * emu_prev + 32];
+  emu_prev = 0;
+}
+#define SM_HOOK_PARK(a) emu_hook_park(a)
 #include "../../smash-paper_amd/csrc/mam_sm.hpp"
 
 thread_local dim3 threadIdx, blockIdx, blockDim;
@@ -395,4 +423,12 @@ extern "C" int sm_emu_map(const uint8_t *T, const void *SA, const void *ISA, int
 // decide chains parked in S_ALU since the last reset, by pending action
 extern "C" void sm_emu_park_hist(uint64_t *out, int reset) {
   for (int k = 0; k < 16; ++k) { out[k] = emu_park[k]; if (reset) emu_park[k] = 0; }
+}
+
+// blocks entered [32] and block-to-block edges [33 * 33] since the last reset
+// (layout: emu_edge above)
+extern "C" void sm_emu_paths(uint64_t *regions, uint64_t *edges, int reset) {
+  if (emu_prev) { ++emu_edge[33 * emu_prev]; emu_prev = emu_prev2 = 0; }   // the last iteration's end
+  for (int k = 0; k < 32; ++k) { regions[k] = emu_region_n[k]; if (reset) emu_region_n[k] = 0; }
+  for (int k = 0; k < 33 * 33; ++k) { edges[k] = emu_edge[k]; if (reset) emu_edge[k] = 0; }
 }

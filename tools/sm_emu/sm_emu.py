@@ -199,3 +199,32 @@ class Emu:
             if ws[42 + k]:
                 self.states["CMP." + nm] = int(ws[42 + k])
         return res, iters
+
+
+# SM_REGION numbers of the consume and decide blocks (mam_sm.hpp), and the two
+# pseudo-targets of sm_emu_paths' edges
+BLOCKS = {1: "S_ALU", 2: "S_COPY", 3: "S_BM", 4: "S_KT", 5: "S_IDX", 6: "S_BYTE", 7: "S_CMP",
+          8: "S_USCAN", 9: "S_EX", 10: "A_BS", 11: "A_BS_DONE", 12: "A_XL_DONE", 13: "A_RUN_DONE",
+          14: "A_CHAIN_DONE", 15: "A_EXPAND", 16: "A_AFTER", 17: "A_TOP", 18: "A_TRAV",
+          19: "A_DONE", 28: "A_BSP", 29: "A_EXS", 30: "A_EMIT"}
+END, RESET, PARK = "END", "A_TOPR", "PARK"
+
+
+def paths(reset=True):
+    """(blocks entered {name: n}, edges {(from, to): n}) since the last reset:
+    to is the block entered next in the same iteration, END (the iteration
+    ended after `from`: it named a probe or finished the read), PARK (the
+    chain went backwards and parked in S_ALU) or A_TOPR (`from` sent the lane
+    to A_TOP through the root reset)."""
+    reg = np.zeros(32, np.uint64)
+    edg = np.zeros(33 * 33, np.uint64)
+    lib().sm_emu_paths(reg.ctypes.data_as(C.c_void_p), edg.ctypes.data_as(C.c_void_p), int(reset))
+    to_name = dict(BLOCKS)
+    to_name.update({0: END, 31: RESET, 32: PARK})
+    blocks = {nm: int(reg[k]) for k, nm in BLOCKS.items()}
+    edges = {}
+    for f, fn in BLOCKS.items():
+        for t, tn in to_name.items():
+            if edg[33 * f + t]:
+                edges[(fn, tn)] = int(edg[33 * f + t])
+    return blocks, edges
