@@ -45,7 +45,7 @@ void free_index(smash_index *ix) {
   dfree(ix->d_ovf); dfree(ix->d_map); dfree(ix->d_startpos); dfree(ix->d_sizes);
   dfree(ix->d_uniq); dfree(ix->d_kmer); dfree(ix->d_bitmap); dfree(ix->d_work); dfree(ix->d_rec);
   dfree(ix->d_nsdir);
-  smash::release_uniq_scratch(ix);   // (its scratch and second stream)
+  smash::release_uniq_scratch(ix);
   (void)hipSetDevice(cur);
   delete ix;
 }

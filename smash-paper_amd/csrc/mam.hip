@@ -20,16 +20,16 @@
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
-#include <cstring>
 
 namespace smash {
 namespace {
 
+// SMASH_MODE_MAM_PLAIN: the reference's probe sequence, one read per lane.
 // Persistent grid sized to the resident capacity; each lane pulls the next
 // read from a device work counter as soon as its previous read is done, so a
 // slow read (repeats: large intervals) delays only its own lane instead of a
 // whole block.  The read is copied into the lane's LDS row.
-template <class IdxT, int BLOCK, bool PLAIN>
+template <class IdxT, int BLOCK>
 __global__ __launch_bounds__(BLOCK) void k_mam(
     DevIndex<IdxT> x, const uint8_t *__restrict__ seqs, uint64_t stride,
     const uint16_t *__restrict__ lens, uint32_t len0, uint64_t n_reads,
@@ -56,15 +56,13 @@ __global__ __launch_bounds__(BLOCK) void k_mam(
       }
     }
     MatchSink sink{out + r * cap, cap, 0};
-    if (PLAIN) mam_read_plain(x, P, L, min_len, sink);
-    else mam_read_v3(x, P, L, min_len, sink);
+    mam_read_plain(x, P, L, min_len, sink);
     n_out[r] = sink.n;
   }
 }
 
-// SMASH_MODE_MAM default: the state-machine kernel (mam_sm.hpp).  Setting
-// SMASH_MAM_KERNEL=direct selects the direct per-lane v3 kernel instead (same
-// results; kept for A/B measurement).
+// SMASH_MODE_MAM: the state-machine kernel (mam_sm.hpp); its algorithm is
+// stated straight-line by orc_mam_v3 (oracle/smash_oracle.c).
 // 64-lane blocks: the LDS row of a lane is its read (40 words at 150 bp), so
 // 16 blocks (4 waves per SIMD, the VGPR limit) fit the CU's 160 KB.
 constexpr int kSmBlock = 64;
@@ -299,25 +297,20 @@ int launch_sm(const smash_index *ix, uint32_t min_len, const uint8_t *seqs,
   return run_sm<IdxT, false, true>(ix, c, n_reads, lds, s, sync_check);
 }
 
-bool use_direct() {
-  const char *e = std::getenv("SMASH_MAM_KERNEL");
-  return e && std::strcmp(e, "direct") == 0;
-}
-
-template <class IdxT, bool PLAIN>
-int launch(const smash_index *ix, uint32_t min_len, const uint8_t *seqs,
+template <class IdxT>
+int launch_plain(const smash_index *ix, uint32_t min_len, const uint8_t *seqs,
            uint64_t stride, const uint16_t *lens, uint32_t len,
            uint64_t n_reads, uint64_t *out, uint32_t cap, uint32_t *n_out,
            hipStream_t s) {
   constexpr int B = 128;
   uint32_t maxL = lens ? 255 : len;
-  uint32_t row = (maxL + 3) / 4 + 1;   // +1 word: lds_load8 over-read
+  uint32_t row = (maxL + 3) / 4 + 1;   // +1 word of padding
   if ((row & 1) == 0) ++row;   // odd word stride: conflict-free LDS rows
   row *= 4;
   const size_t lds = size_t(B) * row + 16;
   int per_cu = 0, cus = 0;
   SMASH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-      &per_cu, reinterpret_cast<const void *>(k_mam<IdxT, B, PLAIN>), B, lds));
+      &per_cu, reinterpret_cast<const void *>(k_mam<IdxT, B>), B, lds));
   SMASH_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ix->device));
   if (per_cu < 1) per_cu = 1;
   uint64_t blocks = uint64_t(per_cu) * uint64_t(cus);
@@ -326,7 +319,7 @@ int launch(const smash_index *ix, uint32_t min_len, const uint8_t *seqs,
   DevIndex<IdxT> x = make_dev_index<IdxT>(ix);
   SMASH_HIP(hipMemsetAsync(ix->d_work, 0, 8, s));
   if (ix->kev[0]) SMASH_HIP(hipEventRecord(ix->kev[0], s));
-  k_mam<IdxT, B, PLAIN><<<unsigned(blocks), B, lds, s>>>(
+  k_mam<IdxT, B><<<unsigned(blocks), B, lds, s>>>(
       x, seqs, stride, lens, len, n_reads, min_len, out, cap, n_out, row,
       reinterpret_cast<unsigned long long *>(ix->d_work));
   SMASH_HIP(hipGetLastError());
@@ -400,27 +393,22 @@ int map_batch_impl(const smash_index *ix, int mode, uint32_t min_len, const uint
   SMASH_HIP(hipSetDevice(ix->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
   const bool plain = mode == SMASH_MODE_MAM_PLAIN;
-  const bool sm_path = !plain && mode != SMASH_MODE_MUM && !use_direct();
+  const bool sm_path = !plain && mode != SMASH_MODE_MUM;
   if (ws && ws->gate && !sm_path) SMASH_HIP(hipStreamWaitEvent(s, ws->gate, 0));   // (launch_sm: after k_prep)
   if (mode == SMASH_MODE_MUM)
     return map_batch_mum(ix, min_len, d_seqs, stride, d_lens, len, n_reads, d_out, cap_per_read,
                          d_n_out, s);
-  if (sm_path) {
-    if (ix->idx_bytes == 4)
-      return launch_sm<uint32_t>(ix, min_len, d_seqs, stride, d_lens, len, n_reads, d_out,
-                                 cap_per_read, d_n_out, s, sync_check, ws);
-    return launch_sm<uint64_t>(ix, min_len, d_seqs, stride, d_lens, len, n_reads, d_out,
-                               cap_per_read, d_n_out, s, sync_check, ws);
-  }
+  if (plain)
+    return ix->idx_bytes == 4
+               ? launch_plain<uint32_t>(ix, min_len, d_seqs, stride, d_lens, len, n_reads, d_out,
+                                        cap_per_read, d_n_out, s)
+               : launch_plain<uint64_t>(ix, min_len, d_seqs, stride, d_lens, len, n_reads, d_out,
+                                        cap_per_read, d_n_out, s);
   if (ix->idx_bytes == 4)
-    return plain ? launch<uint32_t, true>(ix, min_len, d_seqs, stride, d_lens, len, n_reads,
-                                          d_out, cap_per_read, d_n_out, s)
-                 : launch<uint32_t, false>(ix, min_len, d_seqs, stride, d_lens, len, n_reads,
-                                           d_out, cap_per_read, d_n_out, s);
-  return plain ? launch<uint64_t, true>(ix, min_len, d_seqs, stride, d_lens, len, n_reads,
-                                        d_out, cap_per_read, d_n_out, s)
-               : launch<uint64_t, false>(ix, min_len, d_seqs, stride, d_lens, len, n_reads,
-                                         d_out, cap_per_read, d_n_out, s);
+    return launch_sm<uint32_t>(ix, min_len, d_seqs, stride, d_lens, len, n_reads, d_out,
+                               cap_per_read, d_n_out, s, sync_check, ws);
+  return launch_sm<uint64_t>(ix, min_len, d_seqs, stride, d_lens, len, n_reads, d_out,
+                             cap_per_read, d_n_out, s, sync_check, ws);
 }
 
 }  // namespace smash

@@ -4,7 +4,8 @@
 // independent probes, a prefetched SA element), waits for them once, then each
 // lane advances its state with ALU work only until it names its next address.
 //
-// Why: a direct per-lane implementation (mam_read_v3, mam_device.hpp) keeps
+// Why: a direct per-lane implementation (one lane running the algorithm
+// straight through, as k_mam does for the plain search) keeps
 // the lanes of a wave in different phases; SIMT then issues each phase's
 // load for its few lanes only and the wave waits one memory latency per
 // phase present.  Here all lanes share one gather per iteration.  Because the
@@ -19,9 +20,11 @@
 //  * 16-byte scans of U and LCP (singleton chains, expand_link) are unrolled
 //    without branches.
 //
-// The algorithm, and therefore every emitted match, is mam_read_v3's: the
-// same traverse / top_down_faster / (S) scan / (A) extension / (B) chain /
-// suffix link / expand_link / (F) filter decisions, per lane, in order.
+// The algorithm, and therefore every emitted match, is orc_mam_v3's
+// (oracle/smash_oracle.c, its straight-line statement, which the tests
+// compare against): the same traverse / top_down_faster / (S) scan / (A)
+// extension / (B) chain / suffix link / expand_link / (F) filter decisions,
+// per lane, in order.
 #pragma once
 #include "mam_device.hpp"
 

@@ -1,13 +1,19 @@
 // smash-paper_amd/csrc/pipeline.hip -- the read -> bin-count chain per batch.
 //
-//   k_mam        longSA::MAM per mate                        (mam_device.hpp)
-//   k_post       per pair: Aligner::prepare_matches           query.cpp:231-306
-//                + mappability_tag L/R                         mappability_tag.cpp:93-124
+//   k_mam_sm     longSA::MAM per mate                        (mam_sm.hpp, mam.hip)
+//   k_post_fast, per pair: Aligner::prepare_matches           query.cpp:231-306
+//   k_post       + mappability_tag L/R                         mappability_tag.cpp:93-124
 //                + smashMEM filters, key                       smashMEM.py:84-92,154-217
-//   dedup        global first-wins pair key set               smashMEM.py:149,217-228
-//   k_emit       awk/perl extraction of major-chromosome hits smash_mapping.sh:29
-//   k_bin        varbin adjacent de-dup + bisect + count      varbin.py:52-92
+//   k_dedup_claim, k_dedup_decide (keyset.hpp)
+//                global first-wins pair key set               smashMEM.py:149,217-228
+//   k_scan_tiles, k_scan_top, k_scan_apply
+//                per pair: offset of its positions, the position before its first
+//   k_emit_bin_lds + k_bin_reduce (k_emit_bin where the bins do not fit the LDS)
+//                awk/perl extraction of major-chromosome hits smash_mapping.sh:29
+//                + varbin adjacent de-dup + bisect + count    varbin.py:52-92
 //
+// The positions are written out only on demand (smash_pipeline_positions:
+// k_emit); k_bin counts positions given by the caller (smash_bin_positions).
 // All per-pair state lives in HBM; the host only launches.
 #include <hipcub/hipcub.hpp>
 
@@ -91,17 +97,17 @@ struct smash_pipeline {
   hipEvent_t ev_in = nullptr, ev_found[2] = {nullptr, nullptr}, ev_free[2] = {nullptr, nullptr};
   hipEvent_t ev_done = nullptr;   // recorded once at creation: "inputs already complete"
   bool set_used[2] = {false, false};
-  // schedule (read at creation; A/B): SMASH_GATE_POST (default 1) ev_free
-  // is recorded after the batch's whole post stage (single-GPU count path),
-  // so a set's next search starts once that batch is binned: the post stage
-  // of batch b shares the GPU with search b + 1 only, never with b + 2's
-  // (=0: after k_post, the set's match buffers' last reader);
-  // SMASH_GATE_PREP=1 the next search's k_prep also waits for ev_free;
-  // SMASH_ONE_SEARCH=1 a search waits for the other set's (never two
-  // k_mam_sm at once)
-  bool gate_prep = false, gate_post = false, one_search = false;
-  bool found_rec[2] = {false, false};
-  bool defer_free = false;        // count_batch_ev under gate_post
+  // The schedule.  Search b + 1 runs on its own stream beside batch b's post
+  // stage; its k_prep / k_row_lens start at once and the search itself waits
+  // for its set's ev_free.  The single-GPU count path (count_batch_ev)
+  // records ev_free after the batch's whole post stage, so a set's next
+  // search starts once that batch is binned: the post stage of batch b
+  // shares the GPU with search b + 1 only, never with b + 2's.  The phase
+  // calls record it after k_post, the set's match buffers' last reader.
+  // Measured against recording after k_post everywhere, gating k_prep too,
+  // and one search at a time: profiles/r03/sched, profiles/r04/sched
+  // ("Retired alternatives").
+  bool defer_free = false;        // count_batch_ev: it records ev_free itself
   // a search already issued into a set (smash_phase_map_ahead): its reads
   const uint8_t *pref_reads[2] = {nullptr, nullptr};
   uint64_t pref_n[2] = {0, 0};
@@ -127,8 +133,6 @@ struct smash_pipeline {
   size_t scan_temp_bytes = 0;
   uint64_t *d_oslot = nullptr;
   uint64_t oslot_cap = 0;
-  void *d_temp = nullptr;
-  size_t temp_bytes = 0;
   uint64_t *d_table = nullptr;   // {hash hi, arena ref + 1} slots, 0 = empty
   uint64_t table_mask = 0;
   uint64_t *d_arena = nullptr;   // canonical keys: [lo, nk, hit words...] per key
@@ -145,11 +149,11 @@ struct smash_pipeline {
   // fused positions + varbin (k_emit_bin): per pair the pos0 of its last
   // emitted position (-1: none), and its inclusive "last valid" scan
   int64_t *d_lp = nullptr, *d_lps = nullptr;
-  bool fused_bin = true;
   uint32_t bin_flush = 0x8000;    // k_emit_bin_lds's 16-bit counter flush threshold
   uint32_t *d_binpart = nullptr;  // [kBinBlocks][nbins]: k_emit_bin_lds's per-block counts
   bool bin_lds = true;            // k_emit_bin_lds when the bins fit (SMASH_BIN_LDS=0: global
-                                  // atomics; the LDS form runs in the gap SMASH_GATE_POST leaves)
+                                  // atomics; the LDS form runs in the gap the schedule leaves
+                                  // before the set's next search)
   bool pos_dirty = false;         // the positions arrays are not materialised yet
   unsigned long long *d_stats = nullptr;
   uint32_t *d_fb = nullptr;       // [1 + max_pairs]: k_post_fast<16> -> k_post pair list
@@ -828,7 +832,7 @@ __global__ __launch_bounds__(kB) void k_post_fast(PostCfg c, const uint64_t *__r
 }
 
 // ---------------------------------------------------------------------------
-// The two scans of the fused positions path without LDS (hipcub's use LDS and
+// The two scans of the positions phase without LDS (hipcub's use LDS and
 // a decoupled look-back): per pair cnt (u32, inclusive sum -> posoff[q + 1])
 // and lp (i64, inclusive "last valid" -> lps[q]).  A wave owns a tile of
 // kScanTile consecutive pairs, kScanPer per lane; (1) tile aggregates, (2)
@@ -986,12 +990,6 @@ __global__ void k_scan_apply(const uint32_t *__restrict__ cnt, const int64_t *__
   }
 }
 
-__global__ void k_count(const uint8_t *keep, const uint32_t *nmajor, uint64_t n,
-                        uint32_t *cnt) {
-  const uint64_t q = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (q < n) cnt[q] = keep[q] ? nmajor[q] : 0;
-}
-
 __global__ void k_emit(const uint8_t *keep, const int32_t *nk,
                        HitRows hits, const uint32_t *off, uint64_t n,
                        const int64_t *chrom_off, int64_t *pos0, int64_t *absp) {
@@ -1029,11 +1027,6 @@ __device__ __forceinline__ uint32_t bin_of(int64_t a, const int64_t *__restrict_
   }
   return lo == 0 ? nbins - 1 : lo - 1;
 }
-
-// "last valid" scan operator (associative): the right operand unless it is -1
-struct LastValid {
-  __host__ __device__ int64_t operator()(int64_t a, int64_t b) const { return b >= 0 ? b : a; }
-};
 
 // varbin: adjacent de-dup on the pos string (== pos0), bisect_right, count.
 __global__ __launch_bounds__(kB) void k_bin(const int64_t *__restrict__ pos0,
@@ -1268,14 +1261,6 @@ __global__ void k_tail_lps(const uint32_t *npos_p, const int64_t *lps_last, int6
   if (prev && c) prev[0] = last;
 }
 
-__global__ void k_tail(const uint32_t *npos_p, const int64_t *pos0, int64_t *prev,
-                       int64_t *tail) {
-  const uint32_t n = *npos_p;
-  const int64_t last = n ? pos0[n - 1] : -1;
-  if (tail) { tail[0] = int64_t(n); tail[1] = last; }
-  if (prev && n) prev[0] = last;
-}
-
 __global__ void k_reset_prev(int64_t *prev) {
   prev[0] = -1;
   prev[1] = -1;
@@ -1490,15 +1475,8 @@ extern "C" int smash_pipeline_create(const smash_index *ix,
                                                   p->d_boff, nb));
       p->d_scan_temp = dalloc<uint8_t>(p->scan_temp_bytes);
     }
-    size_t b = 0;
     p->d_posoff = dalloc<uint32_t>(P + 1);
     p->d_cnt = dalloc<uint32_t>(P);
-    SMASH_HIPX(hipcub::DeviceScan::InclusiveSum(nullptr, b, p->d_cnt, p->d_posoff + 1, P));
-    size_t c3 = 0;
-    SMASH_HIPX(hipcub::DeviceScan::InclusiveScan(nullptr, c3, static_cast<const int64_t *>(nullptr),
-                                                 static_cast<int64_t *>(nullptr), LastValid(), P));
-    p->temp_bytes = std::max(b, c3);
-    p->d_temp = dalloc<uint8_t>(p->temp_bytes);
     // key records: 2 + nk words each; SMASH reads keep ~7 hits per pair, the
     // arena holds 16 words per key of the capacity (an exhausted arena is a
     // reported error, SMASH_ERR_NOMEM, never a silent cut; refs hold offset
@@ -1515,30 +1493,20 @@ extern "C" int smash_pipeline_create(const smash_index *ix,
     p->d_lp = dalloc<int64_t>(P);
     p->d_lps = dalloc<int64_t>(P);
     {
-      const char *e = getenv("SMASH_FUSED_BIN");   // 0: k_emit + k_bin (A/B)
-      p->fused_bin = !(e && e[0] == '0');
       const char *l = getenv("SMASH_BIN_LDS");   // profiles/r03/binlds: 1.39 vs 2.18 ms
       // (k_emit_bin_lds only where its parts fit: above kBinPartsMax parts,
       // k_emit_bin with global atomics, and no per-block count buffer)
-      p->bin_lds = !(l && l[0] == '0') && p->fused_bin && bin_parts(p->nbins) <= kBinPartsMax;
+      p->bin_lds = !(l && l[0] == '0') && bin_parts(p->nbins) <= kBinPartsMax;
       if (p->bin_lds) p->d_binpart = dalloc<uint32_t>(uint64_t(kBinBlocks) * p->nbins);
       // SMASH_BIN_FLUSH (tests): k_emit_bin_lds's flush threshold, a power of
       // two in [2, 2^15] (default 2^15)
       const char *fl = getenv("SMASH_BIN_FLUSH");
       const unsigned long f = fl ? std::strtoul(fl, nullptr, 10) : 0;
       if (f >= 2 && f <= 0x8000 && !(f & (f - 1))) p->bin_flush = uint32_t(f);
-      auto on = [](const char *v, bool dflt) {
-        const char *x = getenv(v);
-        return x && x[0] ? x[0] == '1' : dflt;
-      };
-      p->gate_prep = on("SMASH_GATE_PREP", false);
-      p->gate_post = on("SMASH_GATE_POST", true);   // profiles/r03/sched: 150.9 vs 160.1 ms
-      p->one_search = on("SMASH_ONE_SEARCH", false);
     }
-    // the positions arrays (2 x 8 B x every hit slot: 26 GB at 6.25 M
-    // pairs) only for the two-kernel path; the fused path writes them when
-    // smash_pipeline_positions asks (ensure_positions)
-    if (!p->fused_bin) SMASH_HIPX(ensure_positions(p));
+    // (the positions arrays, 2 x 8 B x every hit slot = 26 GB at 6.25 M
+    // pairs, are allocated only when smash_pipeline_positions asks:
+    // ensure_positions)
     int64_t init[2] = {-1, -1};
     SMASH_HIPX(hipMemcpy(p->d_prev, init, 16, hipMemcpyHostToDevice));
     p->d_stats = dalloc<unsigned long long>(kStatWords);
@@ -1621,7 +1589,7 @@ extern "C" void smash_pipeline_free(smash_pipeline *p) {
                   (void *)p->d_hash, (void *)p->d_keep, (void *)p->d_bcnt, (void *)p->d_boff,
                   p->d_scan_temp, (void *)p->d_oslot,
                   (void *)p->d_slot, (void *)p->d_contest, (void *)p->d_tsum, (void *)p->d_tlast,
-                  p->d_temp, (void *)p->d_table,
+                  (void *)p->d_table,
                   (void *)p->d_posoff, (void *)p->d_cnt, (void *)p->d_pos0,
                   (void *)p->d_abs, (void *)p->d_prev, (void *)p->d_stats,
                   (void *)p->d_lp, (void *)p->d_lps, (void *)p->d_binpart,
@@ -1638,8 +1606,6 @@ static int search_into(smash_pipeline *p, int k, const uint8_t *d_reads, uint64_
                        hipEvent_t in_ev) {
   hipStream_t xs = p->xs[k];
   SMASH_HIP(hipStreamWaitEvent(xs, in_ev, 0));
-  if (p->one_search && p->found_rec[k ^ 1]) SMASH_HIP(hipStreamWaitEvent(xs, p->ev_found[k ^ 1], 0));
-  if (p->gate_prep && p->set_used[k]) SMASH_HIP(hipStreamWaitEvent(xs, p->ev_free[k], 0));
   // the set's records were last read by its previous search, earlier on xs;
   // its match buffers by that batch's post stage: k_prep runs now, the
   // search after ev_free (SearchWs::gate)
@@ -1666,7 +1632,7 @@ static int search_into(smash_pipeline *p, int k, const uint8_t *d_reads, uint64_
     }
     // the set's lengths were last read by its previous batch's post stage
     // (the records' gate below comes after k_prep: this one before k_row_lens)
-    if (p->set_used[k] && !p->gate_prep) SMASH_HIP(hipStreamWaitEvent(xs, p->ev_free[k], 0));
+    if (p->set_used[k]) SMASH_HIP(hipStreamWaitEvent(xs, p->ev_free[k], 0));
     const bool wide = (reinterpret_cast<uintptr_t>(d_reads) & 15) == 0 && p->stride % 16 == 0 &&
                       p->stride >= ((p->read_len + 15u) & ~15u);
     k_row_lens<<<grid_for(2 * n_pairs, kB, 1u << 30), kB, 0, xs>>>(
@@ -1674,7 +1640,7 @@ static int search_into(smash_pipeline *p, int k, const uint8_t *d_reads, uint64_
     SMASH_HIP(hipGetLastError());
   }
   SearchWs ws{p->d_rec_s[k], p->d_rec_s[k] ? p->rec_bytes : 0, p->d_work_s[k],
-              p->set_used[k] && !p->gate_prep ? p->ev_free[k] : nullptr, p->mhint};
+              p->set_used[k] ? p->ev_free[k] : nullptr, p->mhint};
   ws.geom_len = p->read_len;
   const int rc = map_batch_impl(p->ix, SMASH_MODE_MAM, p->min_len, d_reads, p->stride,
                                 p->var_len ? p->d_len_s[k] : nullptr, p->read_len, 2 * n_pairs,
@@ -1687,7 +1653,6 @@ static int search_into(smash_pipeline *p, int k, const uint8_t *d_reads, uint64_
     p->prof_reads += 2 * n_pairs;
   }
   SMASH_HIP(hipEventRecord(p->ev_found[k], xs));
-  p->found_rec[k] = true;
   p->pref_reads[k] = d_reads;
   p->pref_n[k] = n_pairs;
   p->searched[k] = true;
@@ -1828,38 +1793,24 @@ extern "C" int smash_phase_positions(smash_pipeline *p, int64_t *d_tail, void *s
   hipStream_t s = static_cast<hipStream_t>(stream);
   p->last = s;
   const uint64_t n = p->n_pairs;
-  if (p->fused_bin) {
-    // counts, offsets and each pair's preceding line; the positions
-    // themselves are only written if someone asks (smash_pipeline_positions)
-    if (n) {
-      if (!p->cnt_ready)   // (the multi-GPU path: keep came from the owners)
-        k_count_last<<<grid_for(n, kB, 1u << 30), kB, 0, s>>>(p->d_keep, p->d_nmajor, p->d_nk,
-                                                             hit_rows(p), p->d_chrom_off,
-                                                             n, p->d_cnt, p->d_lp);
-      // posoff (offsets) and lps ("last valid" position), no LDS
-      const uint64_t ntile = (n + kScanTile - 1) / kScanTile;
-      const unsigned g = unsigned((ntile * 64 + kB - 1) / kB);
-      k_scan_tiles<<<g, kB, 0, s>>>(p->d_cnt, p->d_lp, n, p->d_tsum, p->d_tlast);
-      k_scan_top<<<1, 64, 0, s>>>(p->d_tsum, p->d_tlast, ntile);
-      k_scan_apply<<<g, kB, 0, s>>>(p->d_cnt, p->d_lp, n, p->d_tsum, p->d_tlast, p->d_posoff,
-                                    p->d_lps);
-      SMASH_HIP(hipGetLastError());
-      p->pos_dirty = true;
-    }
-    k_tail_lps<<<1, 1, 0, s>>>(p->d_posoff + n, p->d_lps + (n ? n - 1 : 0), nullptr, d_tail);
-    SMASH_HIP(hipGetLastError());
-    return SMASH_OK;
-  }
+  // counts, offsets and each pair's preceding line; the positions
+  // themselves are only written if someone asks (smash_pipeline_positions)
   if (n) {
-    k_count<<<grid_for(n, kB, 1u << 30), kB, 0, s>>>(p->d_keep, p->d_nmajor, n, p->d_cnt);
-    size_t tb = p->temp_bytes;
-    SMASH_HIP(hipcub::DeviceScan::InclusiveSum(p->d_temp, tb, p->d_cnt, p->d_posoff + 1, n, s));
-    k_emit<<<grid_for(n, kB, 1u << 30), kB, 0, s>>>(p->d_keep, p->d_nk, hit_rows(p),
-                                                    p->d_posoff, n,
-                                                    p->d_chrom_off, p->d_pos0, p->d_abs);
+    if (!p->cnt_ready)   // (the multi-GPU path: keep came from the owners)
+      k_count_last<<<grid_for(n, kB, 1u << 30), kB, 0, s>>>(p->d_keep, p->d_nmajor, p->d_nk,
+                                                           hit_rows(p), p->d_chrom_off,
+                                                           n, p->d_cnt, p->d_lp);
+    // posoff (offsets) and lps ("last valid" position), no LDS
+    const uint64_t ntile = (n + kScanTile - 1) / kScanTile;
+    const unsigned g = unsigned((ntile * 64 + kB - 1) / kB);
+    k_scan_tiles<<<g, kB, 0, s>>>(p->d_cnt, p->d_lp, n, p->d_tsum, p->d_tlast);
+    k_scan_top<<<1, 64, 0, s>>>(p->d_tsum, p->d_tlast, ntile);
+    k_scan_apply<<<g, kB, 0, s>>>(p->d_cnt, p->d_lp, n, p->d_tsum, p->d_tlast, p->d_posoff,
+                                  p->d_lps);
+    SMASH_HIP(hipGetLastError());
+    p->pos_dirty = true;
   }
-  p->pos_dirty = false;
-  k_tail<<<1, 1, 0, s>>>(p->d_posoff + n, p->d_pos0, nullptr, d_tail);
+  k_tail_lps<<<1, 1, 0, s>>>(p->d_posoff + n, p->d_lps + (n ? n - 1 : 0), nullptr, d_tail);
   SMASH_HIP(hipGetLastError());
   return SMASH_OK;
 }
@@ -1871,35 +1822,25 @@ extern "C" int smash_phase_bin(smash_pipeline *p, const int64_t *d_prev,
   p->last = s;
   const uint64_t n = p->n_pairs;
   const int64_t *prev = d_prev ? d_prev : p->d_prev;
-  if (p->fused_bin) {
-    const uint32_t parts = bin_parts(p->nbins);
-    if (n && p->bin_lds) {   // (set only when parts <= kBinPartsMax)
-      const uint32_t part = bin_part_size(p->nbins);
-      const unsigned gx = unsigned(std::min<uint64_t>(kBinBlocks, (n + 1023) / 1024));
-      const dim3 grid(gx, parts);
-      k_emit_bin_lds<<<grid, 1024, 0, s>>>(
-          p->d_keep, p->d_nk, hit_rows(p), p->d_chrom_off, p->d_lps, n, prev, p->d_bins,
-          p->nbins, p->d_cell, p->ncell, p->cshift, reinterpret_cast<unsigned long long *>(d_counts),
-          p->d_stats, part, p->bin_flush, p->d_binpart);
-      k_bin_reduce<<<grid_for(p->nbins, kB, 1024), kB, 0, s>>>(
-          p->d_binpart, gx, p->nbins, reinterpret_cast<unsigned long long *>(d_counts));
-    } else if (n) {
-      k_emit_bin<<<grid_for(n, kB, 8192), kB, 0, s>>>(
-          p->d_keep, p->d_nk, hit_rows(p), p->d_chrom_off, p->d_lps, n, prev, p->d_bins,
-          p->nbins, p->d_cell, p->ncell, p->cshift, reinterpret_cast<unsigned long long *>(d_counts),
-          p->d_stats);
-    }
-    // carry the adjacent-dup state across batches (single-GPU use)
-    k_tail_lps<<<1, 1, 0, s>>>(p->d_posoff + n, p->d_lps + (n ? n - 1 : 0), p->d_prev, nullptr);
-    SMASH_HIP(hipGetLastError());
-    return SMASH_OK;
+  const uint32_t parts = bin_parts(p->nbins);
+  if (n && p->bin_lds) {   // (set only when parts <= kBinPartsMax)
+    const uint32_t part = bin_part_size(p->nbins);
+    const unsigned gx = unsigned(std::min<uint64_t>(kBinBlocks, (n + 1023) / 1024));
+    const dim3 grid(gx, parts);
+    k_emit_bin_lds<<<grid, 1024, 0, s>>>(
+        p->d_keep, p->d_nk, hit_rows(p), p->d_chrom_off, p->d_lps, n, prev, p->d_bins,
+        p->nbins, p->d_cell, p->ncell, p->cshift, reinterpret_cast<unsigned long long *>(d_counts),
+        p->d_stats, part, p->bin_flush, p->d_binpart);
+    k_bin_reduce<<<grid_for(p->nbins, kB, 1024), kB, 0, s>>>(
+        p->d_binpart, gx, p->nbins, reinterpret_cast<unsigned long long *>(d_counts));
+  } else if (n) {
+    k_emit_bin<<<grid_for(n, kB, 8192), kB, 0, s>>>(
+        p->d_keep, p->d_nk, hit_rows(p), p->d_chrom_off, p->d_lps, n, prev, p->d_bins,
+        p->nbins, p->d_cell, p->ncell, p->cshift, reinterpret_cast<unsigned long long *>(d_counts),
+        p->d_stats);
   }
-  k_bin<<<2048, kB, 0, s>>>(p->d_pos0, p->d_abs, p->d_posoff + n, prev, p->d_bins,
-                            p->nbins, p->d_cell, p->ncell, p->cshift,
-                            reinterpret_cast<unsigned long long *>(d_counts),
-                            p->d_stats);
   // carry the adjacent-dup state across batches (single-GPU use)
-  k_tail<<<1, 1, 0, s>>>(p->d_posoff + n, p->d_pos0, p->d_prev, nullptr);
+  k_tail_lps<<<1, 1, 0, s>>>(p->d_posoff + n, p->d_lps + (n ? n - 1 : 0), p->d_prev, nullptr);
   SMASH_HIP(hipGetLastError());
   return SMASH_OK;
 }
@@ -1908,7 +1849,7 @@ namespace smash {
 // one batch, its search after in_ev (null: after everything on s so far)
 int count_batch_ev(smash_pipeline *p, const uint8_t *d_reads, uint64_t n_pairs,
                    uint64_t *d_counts, hipStream_t s, hipEvent_t in_ev) {
-  p->defer_free = p->gate_post;
+  p->defer_free = true;   // recorded below, after the batch's whole post stage
   p->keys_bound += n_pairs;
   int rc = phase_map_impl(p, d_reads, n_pairs, s, in_ev);
   p->defer_free = false;
@@ -1918,7 +1859,7 @@ int count_batch_ev(smash_pipeline *p, const uint8_t *d_reads, uint64_t n_pairs,
   if (!rc) rc = smash_phase_bin(p, nullptr, d_counts, s);
   // on every exit once the search is queued: the set's next search must
   // follow whatever of this batch's post stage was queued on s
-  if (p->gate_post && n_pairs && hipEventRecord(p->ev_free[p->set], s) != hipSuccess && !rc) {
+  if (n_pairs && hipEventRecord(p->ev_free[p->set], s) != hipSuccess && !rc) {
     set_error("hipEventRecord failed");
     rc = SMASH_ERR_HIP;
   }
@@ -2514,7 +2455,7 @@ extern "C" int smash_pipeline_positions(smash_pipeline *p, int64_t *h_pos0, int6
                                         uint64_t cap, uint64_t *n_out) {
   if (!p || !n_out) return SMASH_ERR_ARG;
   SMASH_HIP(hipSetDevice(p->device));
-  if (p->pos_dirty && p->n_pairs) {   // fused path: write the last batch's positions now
+  if (p->pos_dirty && p->n_pairs) {   // write the last batch's positions now
     SMASH_HIP(ensure_positions(p));
     k_emit<<<grid_for(p->n_pairs, kB, 1u << 30), kB, 0, p->last>>>(
         p->d_keep, p->d_nk, hit_rows(p), p->d_posoff, p->n_pairs, p->d_chrom_off,

@@ -329,23 +329,36 @@ def test_key_set_exact_under_hash_collisions(gix, tiny_ix, bits, monkeypatch):
 @pytest.mark.parametrize("batch", [7, 1000])
 @pytest.mark.parametrize("s", ["s100", "s150"])
 def test_fused_positions_bins_agree(gix, s, batch, monkeypatch):
-    """k_count_last + k_emit_bin (positions and varbin in one pass; global
-    atomics, and 16-bit LDS counters with the default and a tiny flush
-    threshold) and the two-kernel path (k_emit, then k_bin over the written positions) give the
-    same counts, statistics and, read back after every batch, positions
-    (the adjacent de-dup line carried across batches both ways)."""
+    """The positions phase + k_emit_bin (positions and varbin in one pass;
+    global atomics, and 16-bit LDS counters with the default and a tiny flush
+    threshold) and the two-kernel path through the public calls (k_emit on
+    demand: pipe.positions(), then k_bin over those positions:
+    S.bin_positions, the adjacent de-dup line carried by the caller) give the
+    same counts, statistics and, read back after every batch, positions; the
+    batches' positions, concatenated, are the reference's own positions file."""
     reads = interleaved_reads(s)
     n = reads.shape[0] // 2
 
-    def run():
+    def run(two_kernel=False):
         pipe, starts = make_pipe(gix, reads.shape[1], n)
         counts = torch.zeros(len(starts), dtype=torch.int64, device="cuda")
         pos = []
+        if two_kernel:
+            d_bins = torch.from_numpy(np.ascontiguousarray(starts, np.int64)).cuda()
+            counts2 = torch.zeros(len(starts), dtype=torch.int64, device="cuda")
+            tot, prev = [0, 0, 0], -1
         for b0 in range(0, n, batch):
             b1 = min(n, b0 + batch)
             pipe.count_batch(_device_reads(reads[2 * b0:2 * b1]), b1 - b0, counts)
             p0, pa = pipe.positions()
             pos.append((p0.tolist(), pa.tolist()))
+            if two_kernel and len(p0):
+                st = S.bin_positions(torch.from_numpy(p0).cuda(), torch.from_numpy(pa).cuda(),
+                                     len(p0), prev, d_bins, len(starts), counts2)
+                tot = [x + y for x, y in zip(tot, st)]
+                prev = int(p0[-1])
+        if two_kernel:
+            return counts2.cpu().tolist(), tuple(tot), pos
         return counts.cpu().tolist(), pipe.stats().as_dict(), pos
 
     a = run()
@@ -355,7 +368,13 @@ def test_fused_positions_bins_agree(gix, s, batch, monkeypatch):
     monkeypatch.setenv("SMASH_BIN_FLUSH", "2")   # 16-bit LDS counters flushed every 2
     d = run()
     monkeypatch.delenv("SMASH_BIN_FLUSH")
-    monkeypatch.setenv("SMASH_FUSED_BIN", "0")
-    b = run()
+    b = run(two_kernel=True)
     assert a[1]["error"] == 0
-    assert a == b and a == c and a == d
+    assert a == c and a == d
+    assert b[0] == a[0]
+    assert b[1] == (a[1]["positions"], a[1]["dups"], a[1]["kept"])
+    assert b[2] == a[2]
+    # the batched emit against the reference chain's own output
+    name_at = {v: k for k, v in load_chrom_sizes(gold("tiny_chrom_sizes.txt")).items()}
+    got = ["%s %d" % (name_at[x - p], p) for p0, pa in a[2] for p, x in zip(p0, pa)]
+    assert got == open(gold("%s_positions.txt" % s)).read().splitlines()

@@ -1,7 +1,7 @@
 """tools/pmc_c5_json.py MEASURE_DIR PROFILE_DIR -- profiles/pmc_c5.json: the HBM
 bytes of one C5 rep (smash_mappability_prepare: k_upart1-3, k_nsdir; the scan:
 k_tilebins, k_mapscan, k_mapfix) from the FETCH_SIZE and WRITE_SIZE passes of
-`bench.py --config c5 --steps 1` (tools/r06_run.sh part 4).  The last rep's
+`bench.py --config c5 --steps 1` (profiles/r06/scripts/r06_run.sh part 4).  The last rep's
 dispatches are the ones from the last k_upart1 on.  Every pass of the rep is a
 wide coalesced stream, for which gfx950's FETCH_SIZE reports half the bytes
 (MI355X_MICROARCH.md, HBM/rocprofv3 section): fetched = 2 x FETCH_SIZE;
@@ -37,7 +37,7 @@ def main(mdir, pdir):
            "written_bytes": {k: int(v) for k, v in sorted(wr.items())},
            "method": "2 x FETCH_SIZE (streaming reads: gfx950 counts half) + WRITE_SIZE, per "
                      "kernel of the last rep",
-           "source": "%s/pmc_c5_{FETCH_SIZE,WRITE_SIZE}.csv (rocprofv3 --pmc, tools/r06_run.sh "
+           "source": "%s/pmc_c5_{FETCH_SIZE,WRITE_SIZE}.csv (rocprofv3 --pmc, profiles/r06/scripts/r06_run.sh "
                      "part 4)" % pdir}
     json.dump(out, open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..",
                                      "profiles", "pmc_c5.json"), "w"), indent=1)

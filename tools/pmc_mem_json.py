@@ -1,5 +1,5 @@
 """tools/pmc_mem_json.py MEASURE_DIR PROFILE_DIR -- profiles/pmc_c3mem.json from
-a FETCH_SIZE pass over `bench.py --config c3mem` (tools/r06_run.sh).
+a FETCH_SIZE pass over `bench.py --config c3mem` (profiles/r06/scripts/r06_run.sh).
 
 One MEM launch (smash_match_batch SMASH_MODE_MEM) is k_mem, then the wave
 jobs k_job_slots / k_mem_jobs / k_mem_fix; FETCH_SIZE (kB) of every dispatch
@@ -49,7 +49,7 @@ def main(mdir, pdir, reads=2_000_000):
                 "reads may be up to 2x the figure; below the algorithmic line count, repeat "
                 "families' SA ranges are shared by many reads of a launch (cache hits)",
         "source": os.path.join(pdir, "pmc_fetch_size_mem.csv")
-                  + " (rocprofv3 --pmc FETCH_SIZE over bench.py --config c3mem, tools/r06_run.sh)",
+                  + " (rocprofv3 --pmc FETCH_SIZE over bench.py --config c3mem, profiles/r06/scripts/r06_run.sh)",
     }
     json.dump(out, open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..",
                                      "profiles", "pmc_c3mem.json"), "w"), indent=1)

@@ -58,8 +58,8 @@ def main():
         env = {} if setting == "base" else dict(kv.split("=", 1) for kv in setting.split(","))
         old = {k: os.environ.get(k) for k in env}
         os.environ.update(env)
-        fresh = ("SMASH_POST", "SMASH_BIN", "SMASH_FUSED", "SMASH_KEY", "SMASH_GATE",
-                 "SMASH_ONE", "SMASH_PRIO", "SMASH_PREP_ALL")   # read at create
+        fresh = ("SMASH_POST", "SMASH_BIN", "SMASH_KEY", "SMASH_MAP_HINT",
+                 "SMASH_SEARCH_PRIO")   # read at create
         if any(k.startswith(fresh) for k in env) or pipe is None:
             pipe = None                      # read at create: a fresh pipeline
             pipe = S.Pipeline(dix, cs, starts, L, B, dedup_capacity=P + P // 8 + (1 << 20))
