@@ -269,6 +269,57 @@ int smash_mappability_window(const smash_index *ix, uint64_t begin, uint64_t end
                              uint64_t *lo, uint64_t *hi);
 
 /* ========================================================================== */
+/* Bin design (csrc/bins.hip): the bins.txt / gc.txt table binning.sh reads,  */
+/* which the reference ships for one genome and has no code to make.  A table */
+/* is defined by mappability: with w(g) = 1 iff 1 <= right(g) <= k (the rule  */
+/* of smash_mappability_scan), every bin of a contig holds the same number of */
+/* unique bases, up to one.  The binned contigs (h_chrom_off >= 0, the table  */
+/* of smash_pipeline_cfg) share nbins by largest remainder over their unique  */
+/* bases M, one bin each first; contig c with B bins and M unique bases at    */
+/* ascending positions pos[]: r[j] = j * M / B (j = 0..B), bin 0 starts at 0, */
+/* bin j at pos[r[j]], a bin stops where the next starts, the last at the     */
+/* contig's size.  Rows in contig order, abspos strictly increasing.          */
+/* ========================================================================== */
+typedef struct {
+  uint32_t contig;         /* forward contig index */
+  uint32_t reserved;
+  uint64_t start, stop;    /* [start, stop) on the contig (bins.txt cols 2, 4) */
+  int64_t abspos;          /* h_chrom_off[contig] + start (col 3) */
+  uint64_t n_unique;       /* unique bases of the bin (col 6): r[j + 1] - r[j] */
+  uint64_t n_gc, n_acgt;   /* text bytes c|g and a|c|g|t of the bin (gc.txt) */
+} smash_bin;
+/* Host code: h_bins_per_contig[c] = the bins of contig c out of nbins, from
+ * h_unique[c] (its unique bases): 0 for an unbinned contig, 1 for each binned
+ * one, the other nbins - binned by largest remainder of
+ * (nbins - binned) * M[c] / sum(M) (128-bit product), ties to the earlier
+ * contig.  SMASH_ERR_ARG: fewer bins than binned contigs, or bins left to
+ * share and no unique base at all. */
+int smash_bins_apportion(const uint64_t *h_unique, const int64_t *h_chrom_off,
+                         uint32_t n_contig, uint32_t nbins,
+                         uint32_t *h_bins_per_contig);
+/* The design from raw device arrays: d_map2 = the [left, right] byte pair of
+ * every base of the concatenated forward contigs (a map.bin image + 2),
+ * h_sizes[n_contig] their sizes; d_text + h_text_start[c] = contig c's
+ * lowercase bases (d_text NULL: n_gc = n_acgt = 0).  k in 1..254.  h_out:
+ * nbins rows.  h_contig_unique[n_contig] (or NULL): the unique bases of each
+ * binned contig (0 for the others).  SMASH_ERR_ARG also when a contig gets
+ * more than one bin and more bins than it has unique bases.  Synchronous. */
+int smash_bins_design_raw(int device, const uint8_t *d_map2, const uint8_t *d_text,
+                          uint32_t n_contig, const uint64_t *h_sizes,
+                          const uint64_t *h_text_start, const int64_t *h_chrom_off,
+                          uint32_t k, uint32_t nbins, smash_bin *h_out,
+                          uint64_t *h_contig_unique, void *stream);
+/* The same on an index's own map.bin, text and contig table (4- or 8-byte
+ * elements alike: neither SA nor ISA is read).  SMASH_ERR_ARG for an index
+ * without -rcref / without a map. */
+int smash_bins_design(const smash_index *ix, const int64_t *h_chrom_off, uint32_t k,
+                      uint32_t nbins, smash_bin *h_out, uint64_t *h_contig_unique,
+                      void *stream);
+/* Bases per tile of the design's counting pass (tiles start at each binned
+ * contig's base 0). */
+uint32_t smash_bins_tile(void);
+
+/* ========================================================================== */
 /* Pipeline: prepare_matches (query.cpp:231-306) + mappability_tag           */
 /* (mappability_tag.cpp:93-124) + smashMEM.py filters & global pair de-dup   */
 /* (smashMEM.py:154-228) + varbin.py (varbin.py:52-92), fused per batch.      */

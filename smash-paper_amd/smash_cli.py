@@ -22,6 +22,10 @@ subcommand below takes the same inputs and writes the same files:
   search [-mum|-maxmatch] [-l N] REF.fa QUERY
                                 mummer's match triples for FASTA/FASTQ/SAM queries
                                 (one line per read: name, then ref,query,len)
+  bins NBINS OUTDIR [-k K]      design a bin table for this genome on the device:
+                                OUTDIR/bins.txt and gc.txt as binning.sh reads
+                                them, NBINS bins that each hold the same number
+                                of uniquely mappable K-mer starts (default 36)
   verify [--no-map]             prove the REF.fa.bin/ cache on the device: text
                                 layout, SA / ISA, every LCP value, map.bin (one
                                 JSON report line; exit 1 when it is not the index
@@ -212,6 +216,37 @@ def write_varbin(bins_rows, counts, total, dups, kept, out_path, stats_path):
         o.write("%d\t%d\t%d\t%d\n" % (total, dups, kept, med))
 
 
+# bins.txt (binning.sh:22-24): chr start_chrpos start_abspos stop_chrpos bin_len
+# n_maps_expected
+def write_bins_txt(rows, contigs, path):
+    """rows: a smashgpu.BIN record array (Index.design_bins), contigs: the
+    forward contig names"""
+    with open(path, "w") as o:
+        for r in rows:
+            o.write("%s\t%d\t%d\t%d\t%d\t%d\n" % (contigs[int(r["contig"])], r["start"],
+                                                   r["abspos"], r["stop"],
+                                                   int(r["stop"]) - int(r["start"]),
+                                                   r["n_unique"]))
+
+
+# gc.txt (binning.sh:30-31, read by cbs.r with header=T): chr start stop-1
+# bin_len, then six columns of which cbs.r uses gc.content alone
+GC_HEADER = ("bin.chrom\tbin.start\tbin.end\tbin.length\tgene.count\tcgi.count\t"
+             "dist.telomere\tgc.content\tcviki_count\tnlaiii_count")
+
+
+def write_gc_txt(rows, contigs, path):
+    """gc.content = n_gc / n_acgt of the bin's bases (0.000000 for a bin
+    without an a, c, g or t); the columns binning.sh calls unused are 0"""
+    with open(path, "w") as o:
+        o.write(GC_HEADER + "\n")
+        for r in rows:
+            a, b = int(r["start"]), int(r["stop"])
+            gc = float(int(r["n_gc"])) / float(int(r["n_acgt"])) if int(r["n_acgt"]) else 0.0
+            o.write("%s\t%d\t%d\t%d\t0\t0\t0\t%.6f\t0\t0\n"
+                    % (contigs[int(r["contig"])], a, b - 1, b - a, gc))
+
+
 # ---------------------------------------------------------------------------
 # commands
 # ---------------------------------------------------------------------------
@@ -276,6 +311,21 @@ def cmd_index(args):
             sh.write("@SQ\tSN:%s\tLN:%d\n" % (name, size))
     print("index: N=%d, %.1f GB in HBM, %.1f s" % (ix.N, ix.info.device_bytes / 1e9,
                                                   ix.info.build_seconds), file=sys.stderr)
+
+
+def cmd_bins(args):
+    """design OUTDIR/bins.txt and gc.txt (Index.design_bins); no bad.txt: bad
+    bins are found empirically and binning.sh takes the file as optional"""
+    ref = _ref(args)
+    ix = load_index(ref, args.device)
+    cs = S.read_chrom_sizes(args.chrom_sizes or ref + ".bin/chrom_sizes.txt")
+    try:
+        rows = ix.design_bins(cs, k=args.k, nbins=args.nbins)
+    except S.SmashError as e:
+        raise SystemExit(str(e)) from None
+    os.makedirs(args.outdir, exist_ok=True)
+    write_bins_txt(rows, ix.contigs, os.path.join(args.outdir, "bins.txt"))
+    write_gc_txt(rows, ix.contigs, os.path.join(args.outdir, "gc.txt"))
 
 
 class _Run:
@@ -705,6 +755,13 @@ def main(argv=None):
                            help="distinct pair keys the de-dup set holds (0: sized from "
                                 "the input files)")
         p.set_defaults(fn=fn)
+    p = sub.add_parser("bins", help="design OUTDIR/bins.txt and gc.txt: NBINS bins holding equal "
+                                    "numbers of uniquely mappable K-mer starts")
+    p.add_argument("nbins", type=int)
+    p.add_argument("outdir")
+    p.add_argument("-k", type=int, default=36, help="k-mer length of the mappability (1..254)")
+    p.add_argument("--chrom-sizes", default=None)
+    p.set_defaults(fn=cmd_bins)
     p = sub.add_parser("verify", help="prove REF.fa.bin/ (text layout, SA/ISA, LCP, map.bin) "
                                       "on the device; one JSON report line, exit 1 if not clean")
     p.add_argument("--no-map", action="store_true", help="skip the map.bin recheck")

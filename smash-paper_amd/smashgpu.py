@@ -67,6 +67,7 @@ EXPORTS = [
     "smash_pipeline_reserve_keys", "smash_pipeline_key_capacity", "smash_pipeline_error",
     "smash_mappability_release", "smash_pipeline_map_hints",
     "smash_index_verify", "smash_index_load_verified",
+    "smash_bins_apportion", "smash_bins_design_raw", "smash_bins_design", "smash_bins_tile",
 ]
 
 # smash_index_verify / Index.load(verify=...): the checks to run
@@ -274,6 +275,12 @@ def lib():
     L.smash_count_fastq.argtypes = [vp, C.POINTER(C.c_char_p), C.c_uint32,
                                     C.POINTER(C.c_char_p), C.c_uint32, C.c_int, C.c_uint32, vp,
                                     C.POINTER(FeedStats), vp]
+    L.smash_bins_apportion.argtypes = [u64p, i64p, C.c_uint32, C.c_uint32, u32p]
+    L.smash_bins_design_raw.argtypes = [C.c_int, vp, vp, C.c_uint32, u64p, u64p, i64p, C.c_uint32,
+                                        C.c_uint32, vp, u64p, vp]
+    L.smash_bins_design.argtypes = [vp, i64p, C.c_uint32, C.c_uint32, vp, u64p, vp]
+    L.smash_bins_tile.argtypes = []
+    L.smash_bins_tile.restype = C.c_uint32
     _LIB = L
     return L
 
@@ -281,7 +288,9 @@ def lib():
 def check(rc, what=""):
     if rc != 0:
         msg = lib().smash_last_error().decode(errors="replace")
-        raise SmashError("%s failed (%d): %s" % (what, rc, msg))
+        e = SmashError("%s failed (%d): %s" % (what, rc, msg))
+        e.code = rc
+        raise e
 
 
 def _p(a, t):
@@ -500,6 +509,25 @@ class Index:
             np.bitwise_and(SA, m, out=SA)
             np.bitwise_and(ISA, m, out=ISA)
         return SA, ISA
+
+    def design_bins(self, chrom_sizes_or_off, k=36, nbins=50000, stream=None, unique=False):
+        """smash_bins_design: the variable-width bin table of this genome for
+        k-mers of k bases and nbins bins -- every bin of a contig holds the
+        same number of unique bases, up to one -- as a BIN record array in
+        contig order.  chrom_sizes_or_off: the chrom_sizes dict (binned
+        contigs by contig_tables' rule) or an int64 offset per contig (< 0:
+        not binned).  unique=True: also the unique bases per contig."""
+        if isinstance(chrom_sizes_or_off, dict):
+            off = contig_tables(self.contigs, self.contig_sizes, chrom_sizes_or_off)[2]
+        else:
+            off = np.ascontiguousarray(chrom_sizes_or_off, np.int64)
+        if len(off) != len(self.contigs):
+            raise SmashError("design_bins: %d offsets for %d contigs" % (len(off), len(self.contigs)))
+        out = np.zeros(int(nbins), BIN)
+        M = np.zeros(len(off), np.uint64)
+        check(lib().smash_bins_design(self.h, _p(off, i64p), k, int(nbins), _p(out, vp),
+                                      _p(M, u64p), vp(_stream(stream))), "smash_bins_design")
+        return (out, M) if unique else out
 
     def __del__(self):
         try:
@@ -888,6 +916,59 @@ def mappability_scan(index: Index, begin, end, k=36, d_map_out=None, chrom_off=N
                                        _ptr(d_bin_starts), nbins, _ptr(d_bin_counts),
                                        _ptr(d_contig_counts), vp(_stream(stream))),
           "smash_mappability_scan")
+
+
+# smash_bin (include/smash_gpu.h): one row of a designed bin table
+BIN = np.dtype([("contig", "<u4"), ("reserved", "<u4"), ("start", "<u8"), ("stop", "<u8"),
+                ("abspos", "<i8"), ("n_unique", "<u8"), ("n_gc", "<u8"), ("n_acgt", "<u8")])
+
+
+def bins_tile():
+    """bases per tile of the bin design's counting pass (smash_bins_tile)"""
+    return int(lib().smash_bins_tile())
+
+
+def bins_apportion(unique, chrom_off, nbins):
+    """smash_bins_apportion (host code): the bins of each contig out of nbins
+    from its unique bases -- one per binned contig (offset >= 0), the rest by
+    largest remainder, ties to the earlier contig"""
+    M = np.ascontiguousarray(unique, np.uint64)
+    off = np.ascontiguousarray(chrom_off, np.int64)
+    if len(M) != len(off):
+        raise SmashError("bins_apportion: %d counts for %d offsets" % (len(M), len(off)))
+    out = np.zeros(len(M), np.uint32)
+    check(lib().smash_bins_apportion(_p(M, u64p), _p(off, i64p), len(M), int(nbins),
+                                     _p(out, u32p)), "smash_bins_apportion")
+    return out
+
+
+def bins_design_raw(d_map2, d_text, sizes, text_start, chrom_off, k, nbins, device=0,
+                    stream=None, unique=False):
+    """smash_bins_design_raw: the bin table from a device image of [left,
+    right] byte pairs per base of the concatenated forward contigs (a torch
+    uint8 tensor or a pointer) and, optionally, the lowercase text (contig c
+    at d_text + text_start[c]; None: n_gc = n_acgt = 0).  Returns a BIN record
+    array of nbins rows (with unique=True also the unique bases per contig)."""
+    sz = np.ascontiguousarray(sizes, np.uint64)
+    off = np.ascontiguousarray(chrom_off, np.int64)
+    ts = np.ascontiguousarray(text_start if text_start is not None else np.zeros(len(sz)),
+                              np.uint64)
+    if not (len(sz) == len(off) == len(ts)):
+        raise SmashError("bins_design_raw: sizes, text_start and chrom_off differ in length")
+    if d_map2 is not None and not isinstance(d_map2, int) and \
+            d_map2.numel() * d_map2.element_size() < 2 * int(sz.sum()):
+        raise SmashError("bins_design_raw: the map holds %d bytes, %d bases need %d"
+                         % (d_map2.numel() * d_map2.element_size(), int(sz.sum()),
+                            2 * int(sz.sum())))
+    if d_text is not None and not isinstance(d_text, int) and len(sz) and \
+            d_text.numel() * d_text.element_size() < int((ts + sz).max()):
+        raise SmashError("bins_design_raw: the text ends before a contig does")
+    out = np.zeros(int(nbins), BIN)
+    M = np.zeros(len(sz), np.uint64)
+    check(lib().smash_bins_design_raw(device, _ptr(d_map2), _ptr(d_text), len(sz), _p(sz, u64p),
+                                      _p(ts, u64p), _p(off, i64p), k, int(nbins), _p(out, vp),
+                                      _p(M, u64p), vp(_stream(stream))), "smash_bins_design_raw")
+    return (out, M) if unique else out
 
 
 def mappability_prepare(index: Index, begin, end, stream=None):
