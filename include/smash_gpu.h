@@ -379,9 +379,10 @@ int smash_pipeline_reserve_keys(smash_pipeline *p, uint64_t keys, void *stream);
 /* The keys the set takes for sure (a full set is SMASH_ERR_NOMEM in the
  * pipeline's statistics, never a silent cut). */
 uint64_t smash_pipeline_key_capacity(const smash_pipeline *p);
-/* 1 when the pipeline's searches hand the post stage each forward match's
- * right map.bin byte with the match (from the packed SA word of its row,
- * DESIGN.md section 3), so that byte is not loaded: the index is packed, its
+/* 1 when the pipeline's searches hand the post stage each match's right
+ * map.bin byte with the match (a forward match's from the packed SA word of
+ * its row, a reverse-strand one's from the search's chain scan, DESIGN.md
+ * section 3), so that byte is not loaded: the index is packed, its
  * map.bin was computed from it (not read from a file), and the tag offsets
  * are its contig offsets.  SMASH_MAP_HINT=0 at creation turns it off. */
 int smash_pipeline_map_hints(const smash_pipeline *p);
@@ -567,6 +568,12 @@ int smash_pipeline_peek(smash_pipeline *p, int32_t *h_nk, uint8_t *h_keep,
  * 1 of pair q): what the device read from the rows in variable-length mode,
  * cfg.read_len for each otherwise.  Synchronises. */
 int smash_pipeline_peek_lens(smash_pipeline *p, uint16_t *h_lens);
+/* The same view of the last batch's search output: mate r's h_n[r] match words
+ * (the first min(h_n[r], slots) are stored) in h_words[r * slots ...], as the
+ * search wrote them: ref | qoff << 48 | len << 56, and with map hints
+ * (smash_pipeline_map_hints) a 33-bit ref, the reverse-strand hint in bits
+ * 33..39 and the forward one in bits 40..47.  Synchronises. */
+int smash_pipeline_peek_matches(smash_pipeline *p, uint64_t *h_words, uint32_t *h_n);
 
 /* ========================================================================== */
 /* mapout SAM writer: replaces Aligner::prepare_matches + print_matches       */

@@ -221,8 +221,9 @@ struct SearchWs {
   // buffers' previous reader, so the records of the next batch are built
   // while that reader still runs
   hipEvent_t gate = nullptr;
-  // the pipeline's packed-index searches: match words carry the map hint
-  // (sm::Ctx::mhint; bits 40..47, the post stage masks the reference to 40)
+  // the pipeline's packed-index searches: match words carry the map hints
+  // (sm::Ctx::mhint; bits 40..47 a forward match's, bits 33..39 a reverse
+  // one's; the post stage masks the reference to its 33 position bits)
   bool mhint = false;
   // with d_lens: the longest read of the launch (1..255), which sizes the
   // LDS row and the records; 0: unknown, rows for 255 bases

@@ -572,7 +572,8 @@ struct Ctx {
   // (PK, the read -> bin-count pipeline) each emitted match word carries in
   // bits 40..47 the map.bin right byte m = max(LCP[r], LCP[r + 1]) + 1 of
   // its own SA row r when the word's L8 hints give it exactly (both < 127),
-  // else 0 (csrc/pipeline.hip mate_fast)
+  // else 0, and in bits 33..39 the chain hint (pk_chain_hint), the right
+  // byte of a reverse-strand alignment (csrc/pipeline.hip mate_fast)
   uint32_t mhint;
   uint32_t grab;          // reads a wave claims per atomic on `work` (>= 1)
   uint32_t bm_dual;       // (F) policy: 0 one B-mer per iteration, 1 last + first in one,
@@ -628,6 +629,12 @@ __device__ __forceinline__ uint32_t pk_char(uint32_t q) { return (0x74676361u >>
 __device__ __forceinline__ uint64_t pk_map_hint(uint64_t w) {
   const uint32_t a = uint32_t(w >> 36) & 127u, b = uint32_t(w >> 43) & 127u;
   return (a < 127u && b < 127u) ? uint64_t((a > b ? a : b) + 1u) << 40 : 0ull;
+}
+// the match word's chain hint (bits 33..39, above the packed position): the
+// length m of the shortest unique string ending at the match's last base, when
+// the (B) chain scan found it (hit) and it fits 7 bits; 0: none
+__device__ __forceinline__ uint64_t pk_chain_hint(bool hit, uint32_t m) {
+  return hit && m - 1u < 127u ? uint64_t(m) << kPkPosBits : 0ull;
 }
 // the window's 7 bases as bytes 0..6 of a u64 (byte 7 zero): each 2-bit code
 // spread to a byte selector, one permute of the a c g t table per 4 bytes
@@ -775,7 +782,7 @@ __global__ __launch_bounds__(BLOCK, GEO ? SM_GEO_WPS : 1) void k_mam_sm(const Ct
   // consumed, read by A_EXPAND in the same iteration): the left end stops at
   // start (- 1 with xl1), the right end at end (+ 1 with xr1)
   FlagRef xls{fl, 12}, xl1{fl, 13}, xrs{fl, 14}, xr1{fl, 15};
-  FlagRef em{fl, 16};   // A_EMIT: the singleton at pos is a match to emit
+  FlagRef em{fl, 16};   // A_EMIT: the singleton at pos is a match (A_CHAIN_DONE emits it)
   uint32_t dch = 0, j = 0, thresh = 0, xd = 0;
   uint32_t it = 0;
   uint64_t w_iters = 0, w_active = 0;
@@ -1400,6 +1407,20 @@ __global__ __launch_bounds__(BLOCK, GEO ? SM_GEO_WPS : 1) void k_mam_sm(const Ct
     }
     if (a == A_CHAIN_DONE) {
       SM_REGION(14);
+      // the chain's match (em, from A_EMIT) is stored here, where the scan's
+      // exit is known: j - 1 is the match's last unique suffix (uniqueness is
+      // monotone in the start), so dch - j + 1 is the length of the shortest
+      // unique string ending at the match's last base.  For a match in a
+      // reverse-complement contig that is the map.bin right byte of its
+      // alignment's first forward base (pk_chain_hint; the search does not
+      // know the strand and writes it for every match)
+      if (em) {
+        if (nem < gCap)
+          c.out[rd * gCap + nem] =
+              pack_match(pos & PM, prefix, dch) |
+              (PK && gMh ? pk_map_hint(pos) | pk_chain_hint(hit, dch - j + 1) : 0ull);
+        ++nem;
+      }
       prefix += j;
       if (!hit) {
         a = A_TOPR;
@@ -1658,12 +1679,7 @@ __global__ __launch_bounds__(BLOCK, GEO ? SM_GEO_WPS : 1) void k_mam_sm(const Ct
     }
     if (a == A_EMIT) {                                // (one site: S_BYTE and A_AFTER)
       SM_REGION(30);
-      if (em) {
-        if (nem < gCap)
-          c.out[rd * gCap + nem] =
-              pack_match(pos & PM, prefix, depth) | (PK && gMh ? pk_map_hint(pos) : 0ull);
-        ++nem;
-      }
+      // (em: A_CHAIN_DONE stores the match when this chain's scan ends)
       uscan_start(pos & PM, depth);
       a = A_NONE;
     }

@@ -212,17 +212,19 @@ struct PostCfg {
   // [sp_cell[c], sp_cell[c + 1]] only
   const uint32_t *sp_cell;
   uint32_t sp_shift, sp_ncell;
-  // the search's map hints (SearchWs::mhint): a forward match word carries
-  // its right map.bin byte before the edge rule in bits 40..47 (0: none)
+  // the search's map hints (SearchWs::mhint): a match word carries its
+  // alignment's right map.bin byte before the edge rule, in bits 40..47 if
+  // the match is on the forward strand, in bits 33..39 if on the reverse
+  // strand (0: none)
   bool mhint;
   // variable-length kernels (VAR): the batch's 2 * n_pairs mate lengths
   // (k_row_lens); L above is then the longest a mate can be
   const uint16_t *lens;
 };
 
-// the reference position of a match word: 48 bits (smash_gpu.h), 40 when
-// the word may carry a map hint (N < 2^33 then)
-constexpr uint64_t kRefMask = 0xFFFFFFFFFFull;
+// the reference position of a match word: 48 bits (smash_gpu.h), the packed
+// words' 33 when the word may carry map hints (bits 33..47; N < 2^33 then)
+constexpr uint64_t kRefMask = kPkPosMask;
 
 // A pair's kept hit words (its key, smashMEM.py:122-131): in a dense head row
 // of kHitHead words when it has at most that many (C3: all but a few; 6.7 on
@@ -672,9 +674,14 @@ __device__ __forceinline__ void mate_fast(const PostCfg &c, const uint64_t *__re
   }
   // the alignments (Alignment::resolve) and the addresses of their two map
   // bytes: left at the base after the block's end, right at its first base
-  // (mappability_tag.cpp:98-101), the right one from the search's hint for a
-  // forward match (its own SA row's m, zeroed when m + b >= the contig size,
-  // longSA.cpp:666)
+  // (mappability_tag.cpp:98-101), the right one from the search's hint: m
+  // of the first forward base, zeroed when m + i >= the contig size S, i the
+  // base's offset in its contig (longSA.cpp:666).  A forward match starts at
+  // that base (its own SA row's m, i = ref - start).  A reverse-strand match
+  // at offset o of its contig ends on the base's mirror, i = S - o - len, and
+  // m is the chain hint: the shortest unique string ending there, by the
+  // text's closure under reverse complement the shortest unique one starting
+  // at the base; m + i >= S is m >= o + len
   // (xl / xr: the bytes' map entries minus 2, halved; 0 = none to load)
   uint32_t hint[CAP], xl[CAP], xr[CAP];
 #pragma unroll
@@ -691,8 +698,13 @@ __device__ __forceinline__ void mate_fast(const PostCfg &c, const uint64_t *__re
     A[k] = ok ? (uint64_t(rc) << 63) | (uint64_t(si >> 1) << 48) | (uint64_t(pos) << 16) |
                     (prefix << 8) | len
               : ~0ull;
-    const uint32_t h = c.mhint && !rc ? uint32_t(w[k] >> 40) & 0xFFu : 0u;
-    hint[k] = h ? 0x100u | (ref - spi[k] + h >= sz[k] ? 0u : h) : 0u;
+    // (a reverse-strand match that runs past its contig's end has no mirror
+    // in the forward contig: no hint, the byte is loaded as before)
+    const uint64_t o = ref - spi[k];
+    const uint32_t h = !c.mhint ? 0u : !rc ? uint32_t(w[k] >> 40) & 0xFFu
+                       : o + len <= sz[k] ? uint32_t(w[k] >> kPkPosBits) & 0x7Fu : 0u;
+    const bool edge = rc ? h >= o + len : o + h >= sz[k];
+    hint[k] = h ? 0x100u | (edge ? 0u : h) : 0u;
     // (mapb: an entry past the map reads 0)
     const uint32_t abspos = toff[k] + uint32_t(pos) + 1;
     const uint32_t bl = abspos + uint32_t(prefix) + len - 1, br = abspos + uint32_t(prefix) - 1;
@@ -912,17 +924,33 @@ __global__ void k_scan_tiles(const uint32_t *__restrict__ cnt, const int64_t *__
   }
 }
 
-// one wave: the exclusive prefixes of the ntile aggregates, in place
+// one wave: the exclusive prefixes of the ntile aggregates, in place.  A lane
+// owns a contiguous range and walks it kTopBlk aggregates at a time: the
+// block's loads are issued together and waited for once (one element per trip
+// made each of the range's ~190 trips wait a memory latency of its own)
+constexpr uint32_t kTopBlk = 16;
 __global__ void k_scan_top(uint64_t *tsum, int64_t *tlast, uint64_t ntile) {
   SMASH_BESIDE_SEARCH();
   const uint32_t lane = threadIdx.x & 63;
   const uint64_t per = (ntile + 63) / 64;
-  const uint64_t a = lane * per, b = a + per < ntile ? a + per : ntile;
+  const uint64_t a = lane * per < ntile ? lane * per : ntile;
+  const uint64_t b = a + per < ntile ? a + per : ntile;
   uint64_t s = 0;
   int64_t l = -1;
-  for (uint64_t t = a; t < b; ++t) {
-    s += tsum[t];
-    l = last_valid(l, tlast[t]);
+  for (uint64_t t0 = a; t0 < b; t0 += kTopBlk) {
+    uint64_t ts[kTopBlk];
+    int64_t tl[kTopBlk];
+#pragma unroll
+    for (uint32_t k = 0; k < kTopBlk; ++k) {
+      const bool in = t0 + k < b;
+      ts[k] = in ? tsum[t0 + k] : 0;
+      tl[k] = in ? tlast[t0 + k] : -1;
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < kTopBlk; ++k) {
+      s += ts[k];
+      l = last_valid(l, tl[k]);
+    }
   }
   uint64_t is = s;
   int64_t il = l;
@@ -930,13 +958,24 @@ __global__ void k_scan_top(uint64_t *tsum, int64_t *tlast, uint64_t ntile) {
   uint64_t es = __shfl_up(is, 1, 64);   // exclusive prefix of this lane's range
   int64_t el = __shfl_up(il, 1, 64);
   if (lane == 0) { es = 0; el = -1; }
-  for (uint64_t t = a; t < b; ++t) {
-    const uint64_t ts = tsum[t];
-    const int64_t tl = tlast[t];
-    tsum[t] = es;
-    tlast[t] = el;
-    es += ts;
-    el = last_valid(el, tl);
+  for (uint64_t t0 = a; t0 < b; t0 += kTopBlk) {
+    uint64_t ts[kTopBlk];
+    int64_t tl[kTopBlk];
+#pragma unroll
+    for (uint32_t k = 0; k < kTopBlk; ++k) {
+      const bool in = t0 + k < b;
+      ts[k] = in ? tsum[t0 + k] : 0;
+      tl[k] = in ? tlast[t0 + k] : -1;
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < kTopBlk; ++k) {
+      if (t0 + k < b) {
+        tsum[t0 + k] = es;
+        tlast[t0 + k] = el;
+      }
+      es += ts[k];
+      el = last_valid(el, tl[k]);
+    }
   }
 }
 
@@ -2368,6 +2407,17 @@ extern "C" int smash_pipeline_peek_lens(smash_pipeline *p, uint16_t *h_lens) {
     return SMASH_OK;
   }
   SMASH_HIP(hipMemcpy(h_lens, p->d_lens, 2 * 2 * n, hipMemcpyDeviceToHost));
+  return SMASH_OK;
+}
+
+extern "C" int smash_pipeline_peek_matches(smash_pipeline *p, uint64_t *h_words, uint32_t *h_n) {
+  if (!p || !h_words || !h_n) return SMASH_ERR_ARG;
+  SMASH_HIP(hipSetDevice(p->device));
+  SMASH_HIP(hipDeviceSynchronize());
+  const uint64_t n = p->n_pairs;
+  if (!n) return SMASH_OK;
+  SMASH_HIP(hipMemcpy(h_words, p->d_match, 8 * 2 * n * p->slots, hipMemcpyDeviceToHost));
+  SMASH_HIP(hipMemcpy(h_n, p->d_nmatch, 4 * 2 * n, hipMemcpyDeviceToHost));
   return SMASH_OK;
 }
 

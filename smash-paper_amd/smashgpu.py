@@ -48,7 +48,7 @@ EXPORTS = [
     "smash_phase_map", "smash_phase_export", "smash_dedup_owner",
     "smash_phase_import", "smash_phase_positions", "smash_phase_bin",
     "smash_pipeline_stats", "smash_pipeline_reset", "smash_pipeline_reset_ex", "smash_pipeline_reads_resident", "smash_pipeline_peek",
-    "smash_pipeline_var_len", "smash_pipeline_peek_lens",
+    "smash_pipeline_var_len", "smash_pipeline_peek_lens", "smash_pipeline_peek_matches",
     "smash_pipeline_profile", "smash_pipeline_profile_read",
     "smash_pipeline_positions", "smash_bin_positions", "smash_mappability_scan",
     "smash_sam_records", "smash_sam_format", "smash_sam_free",
@@ -752,7 +752,7 @@ class Pipeline:
 
     @property
     def map_hints(self):
-        """the searches hand forward matches' right map.bin bytes to the post
+        """the searches hand the matches' right map.bin bytes to the post
         stage (smash_pipeline_map_hints)"""
         return bool(lib().smash_pipeline_map_hints(self.h))
 
@@ -840,6 +840,18 @@ class Pipeline:
         check(lib().smash_pipeline_peek_lens(self.h, _p(lens, C.POINTER(C.c_uint16))),
               "smash_pipeline_peek_lens")
         return lens
+
+    def peek_matches(self, n_pairs):
+        """the last batch's raw match words, [2 * n_pairs, slots], and the
+        mates' match counts (smash_pipeline_peek_matches)"""
+        words = np.zeros((2 * n_pairs, self.slots), np.uint64)
+        n = np.zeros(2 * n_pairs, np.uint32)
+        # (declared here: tools/ab.sh also loads builds from before this call)
+        f = lib().smash_pipeline_peek_matches
+        f.argtypes = [vp, u64p, C.POINTER(C.c_uint32)]
+        check(f(self.h, _p(words, u64p), _p(n, C.POINTER(C.c_uint32))),
+              "smash_pipeline_peek_matches")
+        return words, n
 
     def close(self):
         """free the pipeline's device buffers now (its streams are

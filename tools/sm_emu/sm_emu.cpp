@@ -286,6 +286,12 @@ extern "C" int sm_emu_prep(const uint8_t *reads, uint64_t stride, const uint16_t
 static const uint16_t *emu_lens = nullptr;
 extern "C" void sm_emu_set_lens(const uint16_t *lens) { emu_lens = lens; }
 
+// map hints in the match words of the next sm_emu_map calls (Ctx::mhint; the
+// packed instantiation only): off by default, the words then are plain
+// pack_match words
+static int emu_mhint = 0;
+extern "C" void sm_emu_set_mhint(int on) { emu_mhint = on ? 1 : 0; }
+
 template <class IdxT>
 static int run(const uint8_t *T, const void *SA, const void *ISA, const uint8_t *L8,
                const uint8_t *U, const uint64_t *KT, int K, const uint64_t *BM, int B,
@@ -331,7 +337,7 @@ static int run(const uint8_t *T, const void *SA, const void *ISA, const uint8_t 
   sm::bad_table(in_text, &c.bad_tab_lo, &c.bad_tab_hi);
   c.lin_blocks = lin_blocks;
   c.pad = 0;
-  c.mhint = 0;
+  c.mhint = uint32_t(emu_mhint);
   c.grab = 1;
   c.bm_dual = std::getenv("SMASH_SM_BM_DUAL") ? uint32_t(std::atoi(std::getenv("SMASH_SM_BM_DUAL"))) : 3;   // = the device default (mam.hip)
   c.pf = std::getenv("SMASH_SM_PF") ? uint32_t(std::atoi(std::getenv("SMASH_SM_PF"))) : 1;

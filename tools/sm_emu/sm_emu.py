@@ -144,18 +144,23 @@ class Emu:
         self.it = in_text_words(list(ix.acc.in_text))
         self.isz = np.dtype(it).itemsize
 
-    def map(self, reads, min_len=20, cap=512, lin_blocks=8, lens=None):   # = the device default (mam.hip)
+    def map(self, reads, min_len=20, cap=512, lin_blocks=8, lens=None, hints=False):   # = the device default (mam.hip)
         """reads: uint8 [n, L]; lens: uint16 [n], each read's own length (its
         row zero padded past it), as the variable-length pipeline searches:
         through records in the geometry of L.  Returns (list of [(ref, q,
         len)], iterations); self.counters: {array: (16-byte probes, 64-byte
-        line transitions)}."""
+        line transitions)}.  hints (packed only): the search writes its map
+        hints (Ctx::mhint) as the pipeline's searches do; the matches returned
+        are their 33-bit positions, and self.words holds each read's raw match
+        words (forward hint in bits 40..47, chain hint in bits 33..39)."""
+        assert not hints or self.packed
         reads = np.ascontiguousarray(reads, np.uint8)
         n, L = reads.shape
         if lens is not None:
             lens = np.ascontiguousarray(lens, np.uint16)
             assert lens.shape == (n,) and (n == 0 or int(lens.max()) <= L)
         lib().sm_emu_set_lens(lens.ctypes.data_as(C.c_void_p) if lens is not None else None)
+        lib().sm_emu_set_mhint(int(bool(hints)))
         out = np.zeros(n * cap, np.uint64)
         nout = np.zeros(n, np.uint32)
         iters = np.zeros(n, np.uint32)
@@ -175,13 +180,17 @@ class Emu:
             spans.ctypes.data_as(C.c_void_p), viol.ctypes.data_as(C.c_void_p),
             C.c_uint32(lin_blocks), ctr.ctypes.data_as(C.c_void_p), C.c_int(int(self.packed)))
         lib().sm_emu_set_lens(None)
+        lib().sm_emu_set_mhint(0)
         assert rc == 0
         assert viol[0] == 0, ("out-of-range probe", viol.tolist())
         res = []
+        self.words = []
+        rmask = POS_MASK if hints else 0xFFFFFFFFFFFF
         for i in range(n):
             k = min(int(nout[i]), cap)
             w = out[i * cap:i * cap + k]
-            res.append([(int(x & 0xFFFFFFFFFFFF), int((x >> 48) & 0xFF), int(x >> 56)) for x in w])
+            self.words.append(w.copy())
+            res.append([(int(x) & rmask, int((x >> 48) & 0xFF), int(x >> 56)) for x in w])
         self.counters = {name: (int(ctr[k]), int(ctr[8 + k])) for k, name in enumerate(ARRAYS)}
         rq = np.zeros(2, np.uint64)
         lib().sm_emu_requests(rq.ctypes.data_as(C.c_void_p))
