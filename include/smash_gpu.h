@@ -341,8 +341,14 @@ typedef struct {
   const int64_t *h_bin_starts;   /* [nbins] bins.txt col 3 (start abspos), ascending */
   int32_t min_excess;        /* smashMEM arg 5 (smash_mapping.sh:25: 4) */
   int64_t hit_window;        /* smashMEM arg 4 (10000) */
-  uint64_t dedup_capacity;   /* distinct pair keys the persistent set holds
-                                (exact keys: ~16 hit words per key of arena) */
+  uint64_t dedup_capacity;   /* pair keys the persistent set holds (exact keys).
+                                Single GPU: the pairs of a run between two
+                                resets, duplicates and unkeyed pairs included
+                                (every pair keeps a 128-byte key row for the
+                                run); a run that outgrows it grows the set
+                                (see smash_pipeline_reserve_keys).  An owner
+                                of the multi-GPU exchange: distinct keys,
+                                ~16 hit words per key of arena */
   uint32_t read_stride;      /* bytes from one mate to the next in d_reads: 0 or
                                 read_len (dense), or smash_read_stride(read_len):
                                 the device's native rows (16-byte aligned d_reads,
@@ -374,7 +380,11 @@ void smash_pipeline_free(smash_pipeline *p);
  * multi-GPU driver sizes each owner's set from the run's pair count and the
  * owner skew of its first batch (dist.py); smash_count_fastq grows the
  * single-GPU set as its batches arrive (a gzip input's pair count is not
- * known before it is inflated). */
+ * known before it is inflated); the single-GPU batch calls
+ * (smash_count_batch[es], smash_phase_map) do the same themselves, at least
+ * doubling the set, before they queue a batch whose pairs would take the
+ * run past the capacity: such a call then waits for the device once.
+ * Creating the pipeline with the run's pair count avoids it. */
 int smash_pipeline_reserve_keys(smash_pipeline *p, uint64_t keys, void *stream);
 /* The keys the set takes for sure (a full set is SMASH_ERR_NOMEM in the
  * pipeline's statistics, never a silent cut). */

@@ -11,22 +11,41 @@ namespace {
 // The persistent pair-key set of smashMEM.py:149,217-228 (dupeSet), exact:
 // a key is the pair's kept hit list (tid << 48 | pos0 per hit, r1 then r2 in
 // HI order, smashMEM.py:122-131).  Open addressing on the 64-bit hash `hi`;
-// slot = {hi, ref}, ref = epoch << 40 | (1 + arena offset of the key record
-// [lo, nk, words]) (0: the inserting thread has not published it yet).  A
-// hash match counts as the same key only when lo, nk and every hit word
-// agree, so a hash collision is a different key (it goes on probing), never a
-// false duplicate.
+// slot = {hi, ref} (ref 0: the inserting thread has not stored it yet).  A
+// key's record is kept in one of two places, and its ref says which:
+//   * a row ref, g + 1 (bits 39.. clear): the key has at most kHitHead words
+//     and came from pair g of the single-GPU run (pairs counted from the last
+//     reset).  The record is that pair's head row (HitRows, d_hhead) and its
+//     word count (d_nk): both hold every pair of the run, so nothing is
+//     copied.  A smaller g is an earlier pair, in or before the batch, so the
+//     claim's atomicMin alone leaves the slot naming the key's first pair.
+//   * an arena ref, epoch << 40 | kRefPub | (1 + arena offset of the record
+//     [lo, nk, words]): a single-GPU key of more than kHitHead words (its
+//     full row lasts one batch), or a key an owner received (transient
+//     buffers).  Until its decide publishes it, such a key's slot holds its
+//     claim: g + 1 (single GPU) or epoch << 40 | (j + 1) (owner).
+// A hash match counts as the same key only when the word count and every hit
+// word agree (and, against an arena record, the second hash lo), so a hash
+// collision is a different key (it goes on probing), never a false duplicate.
 //
 // Slot accesses are relaxed, with no per-key release / acquire (agent-scope
 // fences write back / invalidate the XCD's L2 on gfx950 and made the round-2
 // insert kernel 5 ms per 2 M pairs): a launch compares only against records
-// of earlier launches, which are visible across the kernel boundary, and
-// against this launch's claims through the claimers' own input rows (the
-// claim / decide kernels below).  Epochs wrap after 2^24 launches.
+// of earlier launches (rows and arena records), which are visible across the
+// kernel boundary, and against this launch's claims through the claimers' own
+// input rows (the claim / decide kernels below).  Epochs run from 1 and wrap
+// after 2^24 launches; a row ref's epoch field is 0.
 constexpr int kRefShift = 40;
-// a published ref (the key's record is in the arena) carries kRefPub; the
-// in-batch claims of k_dedup_claim (pair index + 1, this epoch) do not
+// a published arena ref carries kRefPub; row refs and claims do not
 constexpr uint64_t kRefPub = 1ull << 39;
+// where the claims find the set's records
+struct KeyStore {
+  uint64_t *table;
+  uint64_t mask;
+  const uint64_t *arena;
+  const uint64_t *rows;   // [row_cap][kHitHead]: the run's head rows (d_hhead)
+  const int32_t *row_nk;  // [row_cap]: their word counts (d_nk)
+};
 struct KeyRef {
   const uint64_t *w;   // the key's hit words
   uint32_t nk;
@@ -44,6 +63,16 @@ __device__ bool same_key(const KeyRef &a, const KeyRef &b) {
   if (a.lo != b.lo || a.nk != b.nk) return false;
   for (uint32_t i = 0; i < a.nk; ++i)
     if (a.w[i] != b.w[i]) return false;
+  return true;
+}
+
+// against the row record of the run's pair g (row keys only: a longer key is
+// never equal to one)
+__device__ bool same_key(const KeyStore &st, uint64_t g, const KeyRef &k) {
+  if (k.nk > kHitHead || st.row_nk[g] != int32_t(k.nk)) return false;
+  const uint64_t *r = st.rows + g * kHitHead;
+  for (uint32_t i = 0; i < k.nk; ++i)
+    if (r[i] != k.w[i]) return false;
   return true;
 }
 
@@ -136,35 +165,40 @@ __device__ __forceinline__ void wave_fill_records(uint64_t *arena, uint64_t off,
 // 217-228, first occurrence in pair order wins): two kernels, no LDS, so they
 // run beside the next batch's search.
 //
-// k_dedup_claim: every keyed pair q walks the probe sequence of its hash hi.
-//   * an empty slot: CAS the hi in, then publish ref = epoch << 40 | (q + 1),
-//     a claim of this batch;
-//   * a slot holding hi whose ref is published (kRefPub, an earlier batch's
-//     key): same key (record words compared) -> q is a duplicate of an
-//     earlier batch; else go on probing (a hash collision);
-//   * a slot holding hi claimed in this batch (this epoch, no kRefPub) by pair
-//     q2: same key (q2's hit row compared) -> atomicMin the ref with
-//     epoch << 40 | (q + 1): the slot ends up naming the smallest pair of the
-//     batch with that key; else go on probing.
+// k_dedup_claim: every keyed pair q (pair g = row_base + q of the run) walks
+// the probe sequence of its hash hi.
+//   * an empty slot: CAS the hi in, then store ref = g + 1, its claim;
+//   * a slot holding hi whose ref names a pair of an earlier batch (a row
+//     ref below row_base) or an arena record (kRefPub): same key (that row,
+//     or the record, compared) -> q is a duplicate of an earlier batch; else
+//     go on probing (a hash collision);
+//   * a slot holding hi claimed in this batch by pair q2 (a ref from
+//     row_base on): same key (q2's hit row compared) -> atomicMin the ref
+//     with g + 1: the slot ends up naming the smallest pair of the batch
+//     with that key; else go on probing.
 //   A slot's key never changes once claimed (every pair that lowers its ref
 //   has the claimer's key), so a comparison against whichever pair the ref
 //   names is a comparison against the claimer.  A claim's ref is stored right
 //   after its CAS; a prober that sees the hi before the ref reads the slot
 //   again on its next trip.
 // k_dedup_decide: pair q is kept iff its slot's ref is still its own claim
-//   (the smallest pair of its key in the batch, and the key is new); the
-//   kept pair writes the key's record into the arena and publishes the ref
+//   (the smallest pair of its key in the batch, and the key is new).  A row
+//   key is done with that: the ref already names its record, and the later
+//   batches see it below their row_base.  Only a kept pair of more than
+//   kHitHead words writes its record into the arena and publishes the ref
 //   (kRefPub: never equal to a claim, so the other pairs of the slot, reading
-//   it before or after, all lose).  Fused: k_count_last's per-pair count and
-//   last position.
+//   it before or after, all lose).  Fused: k_count_last's per-pair count; the
+//   last major position is the post stage's (lp), cleared for a pair that
+//   lost.
 // slot_of[q]: the claimed slot, kSlotOld (a key of an earlier batch) or
 // kSlotNone (no key, or the set is full: the error is raised).
 //
 // The owner's first-wins decision of the multi-GPU exchange (k_owner_claim /
 // k_owner_decide) is the same scheme over the received keys: the receive
 // order is the global pair order, so the smallest index j of a key is its
-// first pair.  Both run claim_key / decide_keys below; a key source says
-// where key j of the launch comes from.
+// first pair; every received key's record goes to the arena.  Both run
+// claim_key / decide_keys below; a key source says where key j of the launch
+// comes from and where a kept key's record stays.
 // ---------------------------------------------------------------------------
 constexpr uint64_t kSlotOld = ~0ull, kSlotNone = ~0ull - 1;
 // (single GPU) slot_of flag: the pair's claim filled an empty slot.  Unless
@@ -176,16 +210,29 @@ constexpr uint64_t kSlotOld = ~0ull, kSlotNone = ~0ull - 1;
 constexpr uint64_t kSlotIns = 1ull << 62;
 
 // A key source: count(j) is key j's word count (< 0: j has no key), key(j)
-// the key and, on request, its hash hi; kMarks: its claims mark the slots
-// they fill and the claims they lower (kSlotIns / contest).
+// the key and, on request, its hash hi; claim(j, epoch) the ref of j's claim
+// and claimed(ref, epoch, j2) whether a ref is a claim of this launch, and
+// whose; kMarks: its claims mark the slots they fill and the claims they
+// lower (kSlotIns / contest); in_arena(m): a kept key of m words needs an
+// arena record.
 //
-// the batch's pairs (single GPU): k_post's nk / hash / hit rows
+// the batch's pairs (single GPU): k_post's nk / hash / hit rows, which start
+// at pair row_base of the run's
 struct PairKeys {
   static constexpr bool kMarks = true;
   const int32_t *nk;
   const uint64_t *hash;
   HitRows hits;
   uint8_t *contest;
+  uint64_t row_base;
+  static __device__ __forceinline__ bool in_arena(int32_t m) { return m > int32_t(kHitHead); }
+  __device__ __forceinline__ unsigned long long claim(uint64_t q, uint64_t) const {
+    return row_base + q + 1;
+  }
+  __device__ __forceinline__ bool claimed(unsigned long long ref, uint64_t, uint64_t &q2) const {
+    q2 = ref - 1 - row_base;
+    return (ref >> (kRefShift - 1)) == 0 && ref > row_base;
+  }
   __device__ __forceinline__ int32_t count(uint64_t q) const { return nk[q]; }
   __device__ __forceinline__ KeyRef key(uint64_t q, uint64_t *hi = nullptr) const {
     if (hi) *hi = hash[2 * q];
@@ -203,6 +250,15 @@ struct RecvKeys {
   const uint64_t *recv, *words, *base;
   int world;
   uint64_t hmask;
+  static __device__ __forceinline__ bool in_arena(int32_t) { return true; }
+  __device__ __forceinline__ unsigned long long claim(uint64_t j, uint64_t epoch) const {
+    return (epoch << kRefShift) | (j + 1);
+  }
+  __device__ __forceinline__ bool claimed(unsigned long long ref, uint64_t epoch,
+                                          uint64_t &j2) const {
+    j2 = (ref & (kRefPub - 1)) - 1;
+    return !(ref & kRefPub) && (ref >> kRefShift) == epoch;
+  }
   __device__ __forceinline__ int32_t count(uint64_t j) const {
     return int32_t(recv[kHdrWords * j] >> 40);
   }
@@ -221,12 +277,13 @@ struct RecvKeys {
 // The claim of key j (see above): its slot_of value.  err: the first error
 // of this thread (a full set is SMASH_ERR_NOMEM).
 template <class Src>
-__device__ __forceinline__ uint64_t claim_key(const Src &src, uint64_t j, uint64_t *table,
-                                              uint64_t mask, const uint64_t *arena,
+__device__ __forceinline__ uint64_t claim_key(const Src &src, uint64_t j, const KeyStore &st,
                                               uint64_t epoch, int32_t &err) {
+  uint64_t *const table = st.table;
+  const uint64_t mask = st.mask;
   uint64_t hi = 0;
   const KeyRef me = src.key(j, &hi);
-  const unsigned long long mine = (epoch << kRefShift) | (j + 1);
+  const unsigned long long mine = src.claim(j, epoch);
   uint64_t res = kSlotNone;
   uint64_t i = key_home(hi, mask);
   uint32_t waits = 0;
@@ -256,23 +313,31 @@ __device__ __forceinline__ uint64_t claim_key(const Src &src, uint64_t j, uint64
         }
         continue;
       }
+      uint64_t j2 = 0;
       if (ref & kRefPub) {
         if ((ref >> kRefShift) != epoch &&
-            same_key(arena + ((ref & (kRefPub - 1)) - 1), me)) {
+            same_key(st.arena + ((ref & (kRefPub - 1)) - 1), me)) {
           res = kSlotOld;
           break;
         }
-      } else if ((ref >> kRefShift) == epoch) {
-        const uint64_t j2 = (ref & (kRefPub - 1)) - 1;
+      } else if (src.claimed(ref, epoch, j2)) {
         if (same_key(me, src.key(j2))) {
           if constexpr (Src::kMarks) src.contest[j2] = 1;   // (see kSlotIns)
           atomicMin(sr, mine);
           res = i;
           break;
         }
+      } else if ((ref >> kRefShift) == 0) {
+        // a row ref of an earlier batch.  (A longer key's claim that its
+        // batch could not publish, the arena full and the error raised, has
+        // no record: its word count is above any row key's.)
+        if (same_key(st, ref - 1, me)) {
+          res = kSlotOld;
+          break;
+        }
       }
-      // (an unpublished ref of an earlier epoch: its batch ran out of
-      // arena, an error already raised; no record to compare)
+      // (an owner's unpublished claim of an earlier epoch: its launch ran
+      // out of arena, an error already raised; no record to compare)
     }
     ++probe;
     i = (i + 1) & mask;
@@ -283,9 +348,10 @@ __device__ __forceinline__ uint64_t claim_key(const Src &src, uint64_t j, uint64
 
 // The decision over keys [0, n) (see above): one wave per kDecGroups x 64
 // consecutive keys per trip (wave-wide scans, so every lane of a wave runs
-// every trip).  Winners' records go to the arena and their refs are
-// published; then item(j, win) runs for every j < n.  Returns whether a
-// record of this thread did not fit the arena (SMASH_ERR_NOMEM).
+// every trip).  The winners that need an arena record (Src::in_arena) get it
+// written and their refs published -- the scans and the atomic run only in a
+// wave that holds one; then item(j, win) runs for every j < n.  Returns
+// whether a record of this thread did not fit the arena (SMASH_ERR_NOMEM).
 template <class Src, class Item>
 __device__ __forceinline__ bool decide_keys(const Src &src, uint64_t n, uint64_t *table,
                                             uint64_t *arena, uint64_t arena_cap,
@@ -297,8 +363,8 @@ __device__ __forceinline__ bool decide_keys(const Src &src, uint64_t n, uint64_t
   for (uint64_t c0 = (uint64_t(blockIdx.x) * blockDim.x + (threadIdx.x & ~63u)) * kDecGroups;
        c0 < n; c0 += stride * kDecGroups) {
     bool wins[kDecGroups];
-    uint32_t needs[kDecGroups], incls[kDecGroups], tots[kDecGroups];
-    uint32_t sum = 0;
+    uint32_t needs[kDecGroups];
+    bool rec = false;
 #pragma unroll
     for (uint32_t g = 0; g < kDecGroups; ++g) {
       const uint64_t j = c0 + 64 * g + lane;
@@ -314,104 +380,104 @@ __device__ __forceinline__ bool decide_keys(const Src &src, uint64_t n, uint64_t
           const unsigned long long ref = __hip_atomic_load(
               reinterpret_cast<unsigned long long *>(&table[2 * (sl & ~kSlotIns) + 1]),
               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          win = ref == ((epoch << kRefShift) | (j + 1));
+          win = ref == src.claim(j, epoch);
         }
       }
       wins[g] = win;
-      needs[g] = win ? 2u + uint32_t(m) : 0u;
-      incls[g] = wave_incl(needs[g], tots[g]);
-      sum += tots[g];
+      needs[g] = win && Src::in_arena(m) ? 2u + uint32_t(m) : 0u;
+      rec = rec || needs[g];
     }
-    unsigned long long wbase = 0;
-    if (lane == 63 && sum) wbase = atomicAdd(arena_top, (unsigned long long)sum);
-    wbase = __shfl(wbase, 63, 64);
+    if (__any(rec)) {   // (wave-uniform: every lane is here)
+      uint32_t incls[kDecGroups], tots[kDecGroups];
+      uint32_t sum = 0;
+#pragma unroll
+      for (uint32_t g = 0; g < kDecGroups; ++g) {
+        incls[g] = wave_incl(needs[g], tots[g]);
+        sum += tots[g];
+      }
+      unsigned long long wbase = 0;
+      if (lane == 63) wbase = atomicAdd(arena_top, (unsigned long long)sum);
+      wbase = __shfl(wbase, 63, 64);
+#pragma unroll
+      for (uint32_t g = 0; g < kDecGroups; ++g) {
+        const uint64_t j = c0 + 64 * g + lane;
+        const uint32_t need = needs[g], incl = incls[g], total = tots[g];
+        const uint64_t off = uint64_t(wbase) + incl - need;
+        wbase += total;
+        const bool ok = need && off + need <= arena_cap;
+        KeyRef me{nullptr, 0u, 0ull};
+        if (need) me = src.key(j);
+        wave_fill_records(arena, off, incl, total, ok, me.lo, me.nk, me.w);
+        if (need) {
+          if (!ok) {
+            full = true;   // the slot stays a claim: never matched (no kRefPub)
+          } else {
+            __hip_atomic_store(
+                reinterpret_cast<unsigned long long *>(&table[2 * (slot_of[j] & ~kSlotIns) + 1]),
+                (unsigned long long)((epoch << kRefShift) | kRefPub | (off + 1)),
+                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          }
+        }
+      }
+    }
 #pragma unroll
     for (uint32_t g = 0; g < kDecGroups; ++g) {
       const uint64_t j = c0 + 64 * g + lane;
-      const bool win = wins[g];
-      const uint32_t need = needs[g], incl = incls[g], total = tots[g];
-      const uint64_t off = uint64_t(wbase) + incl - need;
-      wbase += total;
-      const bool ok = win && off + need <= arena_cap;
-      KeyRef me{nullptr, 0u, 0ull};
-      if (win) me = src.key(j);
-      wave_fill_records(arena, off, incl, total, ok, me.lo, me.nk, me.w);
-      if (win) {
-        if (!ok) {
-          full = true;   // the slot stays a claim: never matched (no kRefPub)
-        } else {
-          __hip_atomic_store(
-              reinterpret_cast<unsigned long long *>(&table[2 * (slot_of[j] & ~kSlotIns) + 1]),
-              (unsigned long long)((epoch << kRefShift) | kRefPub | (off + 1)), __ATOMIC_RELAXED,
-              __HIP_MEMORY_SCOPE_AGENT);
-        }
-      }
-      if (j < n) item(j, win);
+      if (j < n) item(j, wins[g]);
     }
   }
   return full;
 }
 
 __global__ void k_dedup_claim(const int32_t *__restrict__ nk, const uint64_t *__restrict__ hash,
-                              HitRows hits, uint64_t n,
-                              uint64_t *table, uint64_t mask, const uint64_t *arena,
+                              HitRows hits, uint64_t n, uint64_t row_base, KeyStore st,
                               uint64_t epoch, uint64_t *slot_of, uint8_t *contest,
                               unsigned long long *stats) {
   SMASH_BESIDE_SEARCH();
-  const PairKeys src{nk, hash, hits, contest};
+  const PairKeys src{nk, hash, hits, contest, row_base};
   const uint64_t stride = uint64_t(gridDim.x) * blockDim.x;
   int32_t err = 0;
   for (uint64_t q = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; q < n; q += stride)
-    if (nk[q] >= 0) slot_of[q] = claim_key(src, q, table, mask, arena, epoch, err);
+    if (nk[q] >= 0) slot_of[q] = claim_key(src, q, st, epoch, err);
   if (err) atomicCAS(&stats[S_ERR], 0ull, (unsigned long long)(unsigned)err);
 }
 
+// lp: in, each pair's last major position or -1 (the post stage's); out, -1
+// for the pairs that lost
 __global__ void k_dedup_decide(const int32_t *__restrict__ nk, const uint64_t *__restrict__ hash,
-                               HitRows hits,
-                               const uint32_t *__restrict__ nmajor,
-                               const int64_t *__restrict__ chrom_off, uint64_t n,
-                               uint64_t *table, uint64_t *arena, uint64_t arena_cap,
-                               unsigned long long *arena_top, uint64_t epoch,
+                               HitRows hits, const uint32_t *__restrict__ nmajor, uint64_t n,
+                               uint64_t row_base, uint64_t *table, uint64_t *arena,
+                               uint64_t arena_cap, unsigned long long *arena_top, uint64_t epoch,
                                const uint64_t *__restrict__ slot_of,
                                const uint8_t *__restrict__ contest, uint8_t *keep,
                                uint32_t *cnt, int64_t *lp, unsigned long long *stats) {
   SMASH_BESIDE_SEARCH();
-  const PairKeys src{nk, hash, hits, const_cast<uint8_t *>(contest)};   // (read only here)
+  const PairKeys src{nk, hash, hits, const_cast<uint8_t *>(contest), row_base};   // (read only here)
   unsigned long long kp = 0, dp = 0;
   const bool full = decide_keys(
       src, n, table, arena, arena_cap, arena_top, epoch, slot_of,
       [&](uint64_t q, bool win) __attribute__((always_inline)) {
-        const int32_t m = nk[q];
-        if (m >= 0) {
+        if (nk[q] >= 0) {
           ++kp;
-          dp += win ? 0 : 1;
+          if (!win) {
+            ++dp;
+            lp[q] = -1;
+          }
         }
         keep[q] = win ? 1 : 0;
-        const uint32_t c = win ? nmajor[q] : 0;   // k_count_last
-        cnt[q] = c;
-        int64_t last = -1;
-        if (c) {
-          const uint64_t *h = hits.row(q, m);
-          for (int32_t j = m - 1; j >= 0; --j)
-            if (chrom_off[uint32_t(h[j] >> 48)] >= 0) {
-              last = int64_t(h[j] & 0xFFFFFFFFFFFFull);
-              break;
-            }
-        }
-        lp[q] = last;
+        cnt[q] = win ? nmajor[q] : 0;   // k_count_last
       });
   wave_stats(stats, S_KEYPAIRS, kp, S_DUPEPAIRS, dp, full ? SMASH_ERR_NOMEM : 0);
 }
 
 __global__ void k_owner_claim(const uint64_t *recv, const uint64_t *words, const uint64_t *base,
-                              int world, uint64_t n, uint64_t *table, uint64_t mask,
-                              const uint64_t *arena, uint64_t epoch, uint64_t *slot_of,
-                              unsigned long long *stats, uint64_t hmask) {
+                              int world, uint64_t n, KeyStore st, uint64_t epoch,
+                              uint64_t *slot_of, unsigned long long *stats, uint64_t hmask) {
   const RecvKeys src{recv, words, base, world, hmask};
   const uint64_t stride = uint64_t(gridDim.x) * blockDim.x;
   int32_t err = 0;
   for (uint64_t j = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; j < n; j += stride)
-    slot_of[j] = claim_key(src, j, table, mask, arena, epoch, err);
+    slot_of[j] = claim_key(src, j, st, epoch, err);
   if (err) atomicCAS(&stats[S_ERR], 0ull, (unsigned long long)(unsigned)err);
 }
 
@@ -431,16 +497,22 @@ __global__ void k_owner_decide(const uint64_t *recv, const uint64_t *words, cons
 }  // namespace
 }  // namespace smash
 
-// table slots and arena words for a key set of `keys` keys (at least the
-// batch's max_pairs): 2x the keys in power-of-two slots, 16 words per key
-static void key_set_geometry(uint64_t keys, uint64_t max_pairs, uint64_t *slots,
-                             uint64_t *arena_words) {
-  const uint64_t cap = 2 * std::max<uint64_t>(keys, max_pairs);
+// A key set of `keys` keys (at least the batch's max_pairs): 2x the keys in
+// power-of-two slots, a head row per key (the single-GPU run's pairs), and
+// the arena.  Single GPU, only the keys of more than kHitHead words go to the
+// arena (C3: a few pairs in a million): one word per key of the capacity,
+// a twentieth of the keys at the shortest such record.  An owner's arena
+// holds every key it receives: 16 words per key (SMASH reads keep ~7 hits per
+// pair, a record is 2 + nk words).
+struct KeySetGeometry {
+  uint64_t slots, rows, arena_words, owner_arena_words;
+};
+static KeySetGeometry key_set_geometry(uint64_t keys, uint64_t max_pairs) {
+  const uint64_t k = std::max<uint64_t>(keys, max_pairs);
   uint64_t pw = 1;
-  while (pw < cap) pw <<= 1;
-  *slots = pw;
-  *arena_words = std::min<uint64_t>(16 * std::max<uint64_t>(keys, max_pairs) + (1u << 20),
-                                    smash::kRefPub - 2);
+  while (pw < 2 * k) pw <<= 1;
+  return KeySetGeometry{pw, k, k + (1u << 20),
+                        std::min<uint64_t>(16 * k + (1u << 20), smash::kRefPub - 2)};
 }
 
 // 1 .. 2^24 - 1, never 0 (an unpublished slot)
@@ -451,10 +523,10 @@ static uint64_t next_epoch(smash_pipeline *p) {
 
 // Growth of a set that holds keys: every occupied slot {hash hi, ref} of the
 // old table moves to the first empty slot of its probe sequence in the new
-// one (key_home, linear).  Between batches
-// every ref is published (an arena offset, copied with the arena), so the
-// keys, their records and the first-wins decisions stay as they were; two
-// keys with one hi take two slots, as they did.
+// one (key_home, linear).  Between batches every ref names a record: a pair's
+// row or an arena offset, both copied as they are, so the keys, their records
+// and the first-wins decisions stay as they were; two keys with one hi take
+// two slots, as they did.
 __global__ void k_rehash(const uint64_t *__restrict__ old, uint64_t old_slots, uint64_t *nt,
                          uint64_t mask) {
   const uint64_t stride = uint64_t(gridDim.x) * blockDim.x;

@@ -113,10 +113,18 @@ struct smash_pipeline {
   uint64_t pref_n[2] = {0, 0};
   bool searched[2] = {false, false};
   int set = 1;
-  int32_t *d_nk = nullptr;
+  int32_t *d_nk = nullptr;        // [row_cap], beside d_hhead (below)
   uint32_t *d_nmajor = nullptr;
   uint64_t *d_hits = nullptr;     // [max_pairs][2 * slots]: full hit rows (HitRows)
-  uint64_t *d_hhead = nullptr;    // [max_pairs][kHitHead]: dense head rows
+  // dense head rows and their word counts for every pair of the run, not
+  // only the batch's: [row_cap][kHitHead] and d_nk [row_cap].  A key of at
+  // most kHitHead words stays in its pair's row, which is its record in the
+  // key set (keyset.hpp), so the batch's kernels get the rows from row_base
+  // on (hit_rows, pair_nk) and keep their batch-local pair index.
+  uint64_t *d_hhead = nullptr;
+  uint64_t row_cap = 0;           // pairs the head rows and d_nk hold (>= max_pairs)
+  uint64_t row_base = 0;          // the run's pairs ahead of the current batch
+  uint64_t row_next = 0;          // row_base of the next batch: advanced by dedup_local
   uint64_t *d_hash = nullptr;   // [2*max_pairs] hi, lo
   uint8_t *d_keep = nullptr;
   uint64_t *d_slot = nullptr;     // [max_pairs] k_dedup_claim -> k_dedup_decide
@@ -133,11 +141,15 @@ struct smash_pipeline {
   size_t scan_temp_bytes = 0;
   uint64_t *d_oslot = nullptr;
   uint64_t oslot_cap = 0;
-  uint64_t *d_table = nullptr;   // {hash hi, arena ref + 1} slots, 0 = empty
+  uint64_t *d_table = nullptr;   // {hash hi, ref} slots (keyset.hpp), 0 = empty
   uint64_t table_mask = 0;
-  uint64_t *d_arena = nullptr;   // canonical keys: [lo, nk, hit words...] per key
+  // key records [lo, nk, hit words...]: the single-GPU keys of more than
+  // kHitHead words, and every key an owner received (grown to 16 words per
+  // key by the first smash_dedup_owner)
+  uint64_t *d_arena = nullptr;
   uint64_t arena_cap = 0;        // words
   unsigned long long *d_arena_top = nullptr;
+  bool owner_arena = false;      // smash_dedup_owner has grown the arena to an owner's size
   // pairs de-duplicated since the last reset (single GPU): a bound on the
   // keys the set holds, on the host, for the file feed's growth (ensure_keys)
   uint64_t keys_bound = 0;
@@ -375,8 +387,8 @@ template <bool VAR>
 __device__ __noinline__ void post_pair(const PostCfg &c, const uint64_t *__restrict__ match,
                                        const uint32_t *__restrict__ nmatch, uint64_t q,
                                        int32_t *nk_out, uint32_t *nmajor_out,
-                                       HitRows hits_out, uint64_t *hash_out, int32_t &err,
-                                       unsigned long long &nm, uint8_t *ws) {
+                                       HitRows hits_out, uint64_t *hash_out, int64_t *lp_out,
+                                       int32_t &err, unsigned long long &nm, uint8_t *ws) {
   {
     Aln *a = reinterpret_cast<Aln *>(ws);
     Hit *h1 = reinterpret_cast<Hit *>(ws + uint64_t(c.slots) * sizeof(Aln));
@@ -402,6 +414,7 @@ __device__ __noinline__ void post_pair(const PostCfg &c, const uint64_t *__restr
     uint64_t *ho = hits_out.full + q * (2 * uint64_t(c.slots));
     int32_t nk = -1;
     uint32_t nmaj = 0;
+    int64_t lastp = -1;                      // the last major hit's pos0 (k_dedup_decide's lp)
     uint64_t hh = 0x9E3779B97F4A7C15ull, hl = 0xD1B54A32D192ED03ull;
     if (m1 > 0 || m2 > 0) {                  // smashMEM.py:162
       nk = 0;
@@ -410,7 +423,10 @@ __device__ __noinline__ void post_pair(const PostCfg &c, const uint64_t *__restr
         const uint64_t w = (uint64_t(tid) << 48) ^ uint64_t(pos);
         hh = mix64(hh ^ w) + 0x632BE59BD9B4E019ull;
         hl = mix64(hl + w * 0x9E3779B97F4A7C15ull) ^ (hl >> 29);
-        if (c.chrom_off[tid] >= 0) ++nmaj;
+        if (c.chrom_off[tid] >= 0) {
+          ++nmaj;
+          lastp = int64_t(uint64_t(pos) & 0xFFFFFFFFFFFFull);
+        }
       };
       for (int i = 0; i < m1; ++i) put(h1[i].tid, h1[i].pos);
       for (int b = 0; b < m2; ++b) {         // hit window (smashMEM.py:193-200)
@@ -429,6 +445,7 @@ __device__ __noinline__ void post_pair(const PostCfg &c, const uint64_t *__restr
     }
     nk_out[q] = nk;
     nmajor_out[q] = nmaj;
+    lp_out[q] = lastp;
     hash_out[2 * q] = hh;
     hash_out[2 * q + 1] = hl;
   }
@@ -477,8 +494,8 @@ __global__ __launch_bounds__(kB) void k_post(PostCfg c, const uint64_t *__restri
                                              uint64_t n_pairs, const uint32_t *list,
                                              const uint32_t *n_list, int32_t *nk_out,
                                              uint32_t *nmajor_out, HitRows hits_out,
-                                             uint64_t *hash_out, unsigned long long *stats,
-                                             uint8_t *ws) {
+                                             uint64_t *hash_out, int64_t *lp_out,
+                                             unsigned long long *stats, uint8_t *ws) {
   SMASH_BESIDE_SEARCH();
   int32_t err = 0;
   unsigned long long nm = 0, np = 0;
@@ -487,8 +504,8 @@ __global__ __launch_bounds__(kB) void k_post(PostCfg c, const uint64_t *__restri
   const uint64_t n = list ? *n_list : n_pairs;
   for (uint64_t i = t; i < n; i += uint64_t(gridDim.x) * blockDim.x) {
     unsigned long long m = 0;
-    post_pair<VAR>(c, match, nmatch, list ? list[i] : i, nk_out, nmajor_out, hits_out, hash_out, err,
-              m, my);
+    post_pair<VAR>(c, match, nmatch, list ? list[i] : i, nk_out, nmajor_out, hits_out, hash_out,
+                   lp_out, err, m, my);
     nm += m;
     ++np;
   }
@@ -769,7 +786,7 @@ __global__ __launch_bounds__(kB) void k_post_fast(PostCfg c, const uint64_t *__r
                                                   uint32_t *up_list, uint32_t *up_n,
                                                   int32_t *nk_out, uint32_t *nmajor_out,
                                                   HitRows hits_out, uint64_t *hash_out,
-                                                  unsigned long long *stats) {
+                                                  int64_t *lp_out, unsigned long long *stats) {
   SMASH_BESIDE_SEARCH();
   const uint64_t *sp = c.startpos;
   const uint64_t n = list ? *n_list : n_pairs;
@@ -798,6 +815,7 @@ __global__ __launch_bounds__(kB) void k_post_fast(PostCfg c, const uint64_t *__r
                               : hits_out.full + q * (2 * uint64_t(c.slots));
       int32_t nk = -1;
       uint32_t nmaj = 0;
+      int64_t lastp = -1;                     // the last major hit's pos0 (k_dedup_decide's lp)
       uint64_t hh = 0x9E3779B97F4A7C15ull, hl = 0xD1B54A32D192ED03ull;
       bool any = false;
 #pragma unroll
@@ -811,7 +829,10 @@ __global__ __launch_bounds__(kB) void k_post_fast(PostCfg c, const uint64_t *__r
           const uint64_t x = (uint64_t(tid) << 48) ^ uint64_t(pos);
           hh = mix64(hh ^ x) + 0x632BE59BD9B4E019ull;
           hl = mix64(hl + x * 0x9E3779B97F4A7C15ull) ^ (hl >> 29);
-          if (c.chrom_off[tid] >= 0) ++nmaj;
+          if (c.chrom_off[tid] >= 0) {
+            ++nmaj;
+            lastp = pos;
+          }
         };
 #pragma unroll
         for (int i = 0; i < CAP; ++i)
@@ -836,6 +857,7 @@ __global__ __launch_bounds__(kB) void k_post_fast(PostCfg c, const uint64_t *__r
       }
       nk_out[q] = nk;
       nmajor_out[q] = nmaj;
+      lp_out[q] = lastp;
       hash_out[2 * q] = hh;
       hash_out[2 * q + 1] = hl;
     }
@@ -1351,7 +1373,12 @@ PostCfg post_cfg(const smash_pipeline *p) {
   return c;
 }
 
-HitRows hit_rows(const smash_pipeline *p) { return HitRows{p->d_hhead, p->d_hits, p->slots}; }
+// the current batch's rows and word counts: the run's from row_base on (the
+// full rows are per batch)
+HitRows hit_rows(const smash_pipeline *p) {
+  return HitRows{p->d_hhead + p->row_base * kHitHead, p->d_hits, p->slots};
+}
+int32_t *pair_nk(const smash_pipeline *p) { return p->d_nk + p->row_base; }
 
 }  // namespace
 }  // namespace smash
@@ -1500,10 +1527,12 @@ extern "C" int smash_pipeline_create(const smash_index *ix,
     SMASH_HIPX(hipEventSynchronize(p->ev_done));
     p->d_match = p->d_match_s[0];
     p->d_nmatch = p->d_nmatch_s[0];
-    p->d_nk = dalloc<int32_t>(P);
+    const KeySetGeometry geo = key_set_geometry(cfg->dedup_capacity, P);
+    p->row_cap = geo.rows;
+    p->d_nk = dalloc<int32_t>(p->row_cap);
     p->d_nmajor = dalloc<uint32_t>(P);
     p->d_hits = dalloc<uint64_t>(P * 2 * p->slots);
-    p->d_hhead = dalloc<uint64_t>(P * smash::kHitHead);
+    p->d_hhead = dalloc<uint64_t>(p->row_cap * smash::kHitHead);
     p->d_hash = dalloc<uint64_t>(2 * P);
     p->d_keep = dalloc<uint8_t>(P);
     {   // the multi-GPU export's per-(owner, block) counts, up to 64 owners
@@ -1516,12 +1545,14 @@ extern "C" int smash_pipeline_create(const smash_index *ix,
     }
     p->d_posoff = dalloc<uint32_t>(P + 1);
     p->d_cnt = dalloc<uint32_t>(P);
-    // key records: 2 + nk words each; SMASH reads keep ~7 hits per pair, the
-    // arena holds 16 words per key of the capacity (an exhausted arena is a
-    // reported error, SMASH_ERR_NOMEM, never a silent cut; refs hold offset
-    // + 1 below kRefPub)
-    uint64_t pw = 0;
-    key_set_geometry(cfg->dedup_capacity, P, &pw, &p->arena_cap);
+    // the key set (keyset.hpp): the arena starts at the single-GPU size, the
+    // long keys' (an exhausted arena is a reported error, SMASH_ERR_NOMEM,
+    // never a silent cut; refs hold offset + 1 below kRefPub).
+    // SMASH_KEY_ARENA_WORDS (tests): that size, to meet the error
+    const uint64_t pw = geo.slots;
+    p->arena_cap = geo.arena_words;
+    if (const char *aw = getenv("SMASH_KEY_ARENA_WORDS"))
+      if (*aw) p->arena_cap = std::max<uint64_t>(1, std::strtoull(aw, nullptr, 10));
     p->table_mask = pw - 1;
     p->d_table = dalloc<uint64_t>(2 * pw);
     SMASH_HIPX(hipMemset(p->d_table, 0, 16 * pw));
@@ -1710,19 +1741,21 @@ static int post_stage(smash_pipeline *p, uint64_t n_pairs, hipStream_t s) {
     const PostCfg pc = post_cfg(p);
     k_post_fast<8, VAR><<<grid_for(n_pairs, kB, 1u << 30), kB, 0, s>>>(
         pc, p->d_match, p->d_nmatch, n_pairs, nullptr, nullptr, std::min(8u, p->post_cap),
-        p->d_l16 + 1, p->d_l16, p->d_nk, p->d_nmajor, hit_rows(p), p->d_hash, p->d_stats);
+        p->d_l16 + 1, p->d_l16, pair_nk(p), p->d_nmajor, hit_rows(p), p->d_hash, p->d_lp,
+        p->d_stats);
     SMASH_HIP(hipGetLastError());
     k_post_fast<FCAP, VAR><<<grid_for(n_pairs, kB, 1024), kB, 0, s>>>(
         pc, p->d_match, p->d_nmatch, n_pairs, p->d_l16 + 1, p->d_l16, p->post_cap,
-        p->d_fb + 1, p->d_fb, p->d_nk, p->d_nmajor, hit_rows(p), p->d_hash, p->d_stats);
+        p->d_fb + 1, p->d_fb, pair_nk(p), p->d_nmajor, hit_rows(p), p->d_hash, p->d_lp,
+        p->d_stats);
     SMASH_HIP(hipGetLastError());
     k_post<VAR><<<kPostBlocks, kB, 0, s>>>(post_cfg(p), p->d_match, p->d_nmatch, n_pairs,
-                                           p->d_fb + 1, p->d_fb, p->d_nk, p->d_nmajor, hit_rows(p),
-                                           p->d_hash, p->d_stats, p->d_post_ws);
+                                           p->d_fb + 1, p->d_fb, pair_nk(p), p->d_nmajor, hit_rows(p),
+                                           p->d_hash, p->d_lp, p->d_stats, p->d_post_ws);
   } else {
     k_post<VAR><<<kPostBlocks, kB, 0, s>>>(post_cfg(p), p->d_match, p->d_nmatch, n_pairs, nullptr,
-                                           nullptr, p->d_nk, p->d_nmajor, hit_rows(p), p->d_hash,
-                                           p->d_stats, p->d_post_ws);
+                                           nullptr, pair_nk(p), p->d_nmajor, hit_rows(p), p->d_hash,
+                                           p->d_lp, p->d_stats, p->d_post_ws);
   }
   SMASH_HIP(hipGetLastError());
   return SMASH_OK;
@@ -1743,6 +1776,14 @@ static int phase_map_impl(smash_pipeline *p, const uint8_t *d_reads, uint64_t n_
   if (rc) return rc;
   if (d_next && (rc = check_pipe(p, n_next))) return rc;
   p->last = s;
+  // this batch's rows follow the pairs the set names (dedup_local); they are
+  // there before anything of the batch is queued: growing the set waits for
+  // the device and moves the rows
+  p->row_base = p->row_next;
+  p->n_pairs = 0;
+  if (p->row_base + n_pairs > p->row_cap &&
+      (rc = smash_pipeline_reserve_keys(p, std::max(p->row_base + n_pairs, 2 * p->row_cap), s)))
+    return rc;
   p->n_pairs = n_pairs;
   if (!n_pairs) return SMASH_OK;
   SMASH_HIP(hipSetDevice(p->device));
@@ -1807,6 +1848,14 @@ extern "C" int smash_phase_search_ahead(smash_pipeline *p, const uint8_t *d_read
   return search_into(p, k, d_reads, n_pairs, p->ev_in);
 }
 
+static int grow_key_set(smash_pipeline *p, uint64_t slots, uint64_t rows, uint64_t words,
+                        hipStream_t s);
+
+// where the claim kernels find the set's records (the run's rows, not the batch's)
+static KeyStore key_store(const smash_pipeline *p) {
+  return KeyStore{p->d_table, p->table_mask, p->d_arena, p->d_hhead, p->d_nk};
+}
+
 // single GPU: the persistent set, first occurrence in pair order
 // (k_dedup_claim, k_dedup_decide), and the positions' per-pair counts
 static int dedup_local(smash_pipeline *p, hipStream_t s) {
@@ -1814,16 +1863,20 @@ static int dedup_local(smash_pipeline *p, hipStream_t s) {
   if (!n) return SMASH_OK;
   const uint64_t epoch = next_epoch(p);
   SMASH_HIP(hipMemsetAsync(p->d_contest, 0, n, s));
-  k_dedup_claim<<<grid_for(n, kB, 8192), kB, 0, s>>>(p->d_nk, p->d_hash, hit_rows(p), n,
-                                                     p->d_table, p->table_mask, p->d_arena, epoch,
-                                                     p->d_slot, p->d_contest, p->d_stats);
+  k_dedup_claim<<<grid_for(n, kB, 8192), kB, 0, s>>>(pair_nk(p), p->d_hash, hit_rows(p), n,
+                                                     p->row_base, key_store(p), epoch, p->d_slot,
+                                                     p->d_contest, p->d_stats);
   SMASH_HIP(hipGetLastError());
   k_dedup_decide<<<grid_for((n + kDecGroups - 1) / kDecGroups, kB, 8192), kB, 0, s>>>(
-      p->d_nk, p->d_hash, hit_rows(p), p->d_nmajor, p->d_chrom_off, n, p->d_table,
-      p->d_arena, p->arena_cap, p->d_arena_top, epoch, p->d_slot, p->d_contest, p->d_keep,
-      p->d_cnt, p->d_lp, p->d_stats);
+      pair_nk(p), p->d_hash, hit_rows(p), p->d_nmajor, n, p->row_base, p->d_table, p->d_arena,
+      p->arena_cap, p->d_arena_top, epoch, p->d_slot, p->d_contest, p->d_keep, p->d_cnt,
+      p->d_lp, p->d_stats);
   SMASH_HIP(hipGetLastError());
   p->cnt_ready = true;
+  // the batch's rows are records of the set now: the next batch's rows follow
+  // them (phase_map_impl), while this batch's later stages still read them at
+  // row_base
+  p->row_next = p->row_base + n;
   return SMASH_OK;
 }
 
@@ -1836,7 +1889,7 @@ extern "C" int smash_phase_positions(smash_pipeline *p, int64_t *d_tail, void *s
   // themselves are only written if someone asks (smash_pipeline_positions)
   if (n) {
     if (!p->cnt_ready)   // (the multi-GPU path: keep came from the owners)
-      k_count_last<<<grid_for(n, kB, 1u << 30), kB, 0, s>>>(p->d_keep, p->d_nmajor, p->d_nk,
+      k_count_last<<<grid_for(n, kB, 1u << 30), kB, 0, s>>>(p->d_keep, p->d_nmajor, pair_nk(p),
                                                            hit_rows(p), p->d_chrom_off,
                                                            n, p->d_cnt, p->d_lp);
     // posoff (offsets) and lps ("last valid" position), no LDS
@@ -1867,14 +1920,14 @@ extern "C" int smash_phase_bin(smash_pipeline *p, const int64_t *d_prev,
     const unsigned gx = unsigned(std::min<uint64_t>(kBinBlocks, (n + 1023) / 1024));
     const dim3 grid(gx, parts);
     k_emit_bin_lds<<<grid, 1024, 0, s>>>(
-        p->d_keep, p->d_nk, hit_rows(p), p->d_chrom_off, p->d_lps, n, prev, p->d_bins,
+        p->d_keep, pair_nk(p), hit_rows(p), p->d_chrom_off, p->d_lps, n, prev, p->d_bins,
         p->nbins, p->d_cell, p->ncell, p->cshift, reinterpret_cast<unsigned long long *>(d_counts),
         p->d_stats, part, p->bin_flush, p->d_binpart);
     k_bin_reduce<<<grid_for(p->nbins, kB, 1024), kB, 0, s>>>(
         p->d_binpart, gx, p->nbins, reinterpret_cast<unsigned long long *>(d_counts));
   } else if (n) {
     k_emit_bin<<<grid_for(n, kB, 8192), kB, 0, s>>>(
-        p->d_keep, p->d_nk, hit_rows(p), p->d_chrom_off, p->d_lps, n, prev, p->d_bins,
+        p->d_keep, pair_nk(p), hit_rows(p), p->d_chrom_off, p->d_lps, n, prev, p->d_bins,
         p->nbins, p->d_cell, p->ncell, p->cshift, reinterpret_cast<unsigned long long *>(d_counts),
         p->d_stats);
   }
@@ -2150,7 +2203,7 @@ extern "C" int smash_phase_export(smash_pipeline *p, int world, uint64_t global_
   unsigned long long *cnt = p->h_owner;
   std::fill(cnt, cnt + 128, 0ull);
   if (n) {
-    k_export_count<<<nblk, kB, 0, s>>>(p->d_nk, p->d_hash, n, world, nblk, p->d_bcnt);
+    k_export_count<<<nblk, kB, 0, s>>>(pair_nk(p), p->d_hash, n, world, nblk, p->d_bcnt);
     size_t tb = p->scan_temp_bytes;
     SMASH_HIP(hipcub::DeviceScan::ExclusiveSum(p->d_scan_temp, tb, p->d_bcnt, p->d_boff,
                                                uint64_t(world) * nblk, s));
@@ -2173,7 +2226,7 @@ extern "C" int smash_phase_export(smash_pipeline *p, int world, uint64_t global_
     SMASH_HIP(hipMalloc(&p->d_send_words, 8 * p->send_words_cap));
   }
   if (n)
-    k_export_fill<<<nblk, kB, 0, s>>>(p->d_nk, p->d_hash, hit_rows(p), n, world, nblk,
+    k_export_fill<<<nblk, kB, 0, s>>>(pair_nk(p), p->d_hash, hit_rows(p), n, world, nblk,
                                       p->d_boff, p->d_send_hdr, p->d_send_words, p->d_send_q);
   SMASH_HIP(hipGetLastError());
   *d_send = p->d_send_hdr;
@@ -2215,12 +2268,17 @@ extern "C" int smash_dedup_owner(smash_pipeline *p, const uint64_t *d_recv, uint
     p->oslot_cap = n_recv + n_recv / 4 + 1024;
     SMASH_HIP(hipMalloc(reinterpret_cast<void **>(&p->d_oslot), 8 * p->oslot_cap));
   }
+  if (!p->owner_arena) {   // an owner's arena holds every key: 16 words per key of the capacity
+    p->owner_arena = true;
+    if (int rc = grow_key_set(p, 0, 0, key_set_geometry(p->row_cap, 0).owner_arena_words, s))
+      return rc;
+  }
   SMASH_HIP(hipMemcpyAsync(p->d_recv_base, base, 8 * 2 * 65, hipMemcpyHostToDevice, s));
   SMASH_HIP(hipEventRecord(p->ev_base, s));
   const uint64_t epoch = next_epoch(p);
   k_owner_claim<<<grid_for(n_recv, kB, 8192), kB, 0, s>>>(
-      d_recv, d_recv_words, p->d_recv_base, world, n_recv, p->d_table, p->table_mask, p->d_arena,
-      epoch, p->d_oslot, p->d_stats, p->hash_mask);
+      d_recv, d_recv_words, p->d_recv_base, world, n_recv, key_store(p), epoch, p->d_oslot,
+      p->d_stats, p->hash_mask);
   SMASH_HIP(hipGetLastError());
   k_owner_decide<<<grid_for((n_recv + kDecGroups - 1) / kDecGroups, kB, 8192), kB, 0, s>>>(
       d_recv, d_recv_words, p->d_recv_base, world, n_recv, p->d_table, p->d_arena, p->arena_cap,
@@ -2238,7 +2296,7 @@ extern "C" int smash_phase_import(smash_pipeline *p, const uint8_t *d_flags_back
     k_import<<<grid_for(p->n_export, kB, 1u << 30), kB, 0, s>>>(d_flags_back, p->d_send_q,
                                                                p->n_export, p->d_keep);
   if (p->n_pairs)
-    k_import_stats<<<grid_for(p->n_pairs, kB, 1u << 30), kB, 0, s>>>(p->d_keep, p->d_nk,
+    k_import_stats<<<grid_for(p->n_pairs, kB, 1u << 30), kB, 0, s>>>(p->d_keep, pair_nk(p),
                                                                     p->n_pairs, p->d_stats);
   SMASH_HIP(hipGetLastError());
   return SMASH_OK;
@@ -2285,7 +2343,7 @@ extern "C" int smash_pipeline_peek(smash_pipeline *p, int32_t *h_nk, uint8_t *h_
   SMASH_HIP(hipDeviceSynchronize());
   const uint64_t n = p->n_pairs;
   if (!n) return SMASH_OK;
-  if (h_nk) SMASH_HIP(hipMemcpy(h_nk, p->d_nk, 4 * n, hipMemcpyDeviceToHost));
+  if (h_nk) SMASH_HIP(hipMemcpy(h_nk, pair_nk(p), 4 * n, hipMemcpyDeviceToHost));
   if (h_keep) SMASH_HIP(hipMemcpy(h_keep, p->d_keep, n, hipMemcpyDeviceToHost));
   if (h_hits) {
     // the ABI's layout, [n][2 * slots] words: the full rows, with the pairs
@@ -2294,8 +2352,9 @@ extern "C" int smash_pipeline_peek(smash_pipeline *p, int32_t *h_nk, uint8_t *h_
     SMASH_HIP(hipMemcpy(h_hits, p->d_hits, 8 * n * W, hipMemcpyDeviceToHost));
     std::vector<int32_t> nk(n);
     std::vector<uint64_t> head(n * smash::kHitHead);
-    SMASH_HIP(hipMemcpy(nk.data(), p->d_nk, 4 * n, hipMemcpyDeviceToHost));
-    SMASH_HIP(hipMemcpy(head.data(), p->d_hhead, 8 * n * smash::kHitHead, hipMemcpyDeviceToHost));
+    SMASH_HIP(hipMemcpy(nk.data(), pair_nk(p), 4 * n, hipMemcpyDeviceToHost));
+    SMASH_HIP(hipMemcpy(head.data(), hit_rows(p).head, 8 * n * smash::kHitHead,
+                        hipMemcpyDeviceToHost));
     for (uint64_t q = 0; q < n; ++q)
       if (nk[q] > 0 && nk[q] <= int32_t(smash::kHitHead))
         std::memcpy(h_hits + q * W, head.data() + q * smash::kHitHead, 8 * size_t(nk[q]));
@@ -2304,42 +2363,77 @@ extern "C" int smash_pipeline_peek(smash_pipeline *p, int32_t *h_nk, uint8_t *h_
   return SMASH_OK;
 }
 
-extern "C" int smash_pipeline_reserve_keys(smash_pipeline *p, uint64_t keys, void *stream) {
-  if (!p) return SMASH_ERR_ARG;
-  uint64_t slots = 0, words = 0;
-  key_set_geometry(keys, p->max_pairs, &slots, &words);
-  slots = std::max<uint64_t>(slots, p->table_mask + 1);
-  words = std::max<uint64_t>(words, p->arena_cap);
-  if (slots <= p->table_mask + 1 && words <= p->arena_cap) return SMASH_OK;
+// The key set with at least `slots` table slots, head rows (and word counts)
+// for `rows` pairs and `words` arena words: the parts that grow are allocated
+// anew and what the set holds moves (slots rehashed; rows, counts and arena
+// words copied as they are), so the refs stay valid.  Synchronous.
+static int grow_key_set(smash_pipeline *p, uint64_t slots, uint64_t rows, uint64_t words,
+                        hipStream_t s) {
+  const uint64_t old_slots = p->table_mask + 1;
+  slots = std::max(slots, old_slots);
+  rows = std::max(rows, p->row_cap);
+  words = std::max(words, p->arena_cap);
+  if (slots == old_slots && rows == p->row_cap && words == p->arena_cap) return SMASH_OK;
   SMASH_HIP(hipSetDevice(p->device));
   SMASH_HIP(hipDeviceSynchronize());   // (no kernel may hold the old set)
   unsigned long long top = 0;
   SMASH_HIP(hipMemcpy(&top, p->d_arena_top, 8, hipMemcpyDeviceToHost));
-  uint64_t *t = nullptr, *a = nullptr;
-  if (hipMalloc(reinterpret_cast<void **>(&t), 16 * slots) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void **>(&a), 8 * words) != hipSuccess) {
+  uint64_t *t = nullptr, *a = nullptr, *h = nullptr;
+  int32_t *k = nullptr;
+  if ((slots > old_slots && hipMalloc(reinterpret_cast<void **>(&t), 16 * slots) != hipSuccess) ||
+      (words > p->arena_cap && hipMalloc(reinterpret_cast<void **>(&a), 8 * words) != hipSuccess) ||
+      (rows > p->row_cap &&
+       (hipMalloc(reinterpret_cast<void **>(&h), 8 * rows * smash::kHitHead) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void **>(&k), 4 * rows) != hipSuccess))) {
     (void)hipFree(t);
-    set_error("smash_pipeline_reserve_keys: out of device memory for " + std::to_string(keys) +
+    (void)hipFree(a);
+    (void)hipFree(h);
+    (void)hipFree(k);
+    set_error("smash_pipeline_reserve_keys: out of device memory for " + std::to_string(rows) +
               " keys");
     return SMASH_ERR_NOMEM;
   }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  SMASH_HIP(hipMemsetAsync(t, 0, 16 * slots, s));
-  if (top) {   // the keys move: arena words as they are, slots rehashed
-    SMASH_HIP(hipMemcpyAsync(a, p->d_arena, 8 * std::min<uint64_t>(top, p->arena_cap),
-                             hipMemcpyDeviceToDevice, s));
-    const uint64_t old_slots = p->table_mask + 1;
+  if (t) {
+    SMASH_HIP(hipMemsetAsync(t, 0, 16 * slots, s));
     k_rehash<<<grid_for(old_slots, 256, 1u << 16), 256, 0, s>>>(p->d_table, old_slots, t, slots - 1);
     SMASH_HIP(hipGetLastError());
   }
+  if (a && top)
+    SMASH_HIP(hipMemcpyAsync(a, p->d_arena, 8 * std::min<uint64_t>(top, p->arena_cap),
+                             hipMemcpyDeviceToDevice, s));
+  // the rows up to the current batch's end (row_next: the pairs the set names;
+  // the current batch's may still be read by its later stages)
+  const uint64_t held = std::min(p->row_cap, std::max(p->row_next, p->row_base + p->n_pairs));
+  if (h && held) {
+    SMASH_HIP(hipMemcpyAsync(h, p->d_hhead, 8 * held * smash::kHitHead, hipMemcpyDeviceToDevice, s));
+    SMASH_HIP(hipMemcpyAsync(k, p->d_nk, 4 * held, hipMemcpyDeviceToDevice, s));
+  }
   SMASH_HIP(hipStreamSynchronize(s));
-  SMASH_HIP(hipFree(p->d_table));
-  SMASH_HIP(hipFree(p->d_arena));
-  p->d_table = t;
-  p->d_arena = a;
-  p->table_mask = slots - 1;
-  p->arena_cap = words;
+  if (t) {
+    SMASH_HIP(hipFree(p->d_table));
+    p->d_table = t;
+    p->table_mask = slots - 1;
+  }
+  if (a) {
+    SMASH_HIP(hipFree(p->d_arena));
+    p->d_arena = a;
+    p->arena_cap = words;
+  }
+  if (h) {
+    SMASH_HIP(hipFree(p->d_hhead));
+    SMASH_HIP(hipFree(p->d_nk));
+    p->d_hhead = h;
+    p->d_nk = k;
+    p->row_cap = rows;
+  }
   return SMASH_OK;
+}
+
+extern "C" int smash_pipeline_reserve_keys(smash_pipeline *p, uint64_t keys, void *stream) {
+  if (!p) return SMASH_ERR_ARG;
+  const KeySetGeometry g = key_set_geometry(keys, p->max_pairs);
+  return grow_key_set(p, g.slots, g.rows, p->owner_arena ? g.owner_arena_words : g.arena_words,
+                      static_cast<hipStream_t>(stream));
 }
 
 namespace smash {
@@ -2353,8 +2447,11 @@ int ensure_keys(smash_pipeline *p, uint64_t n_next, hipStream_t s) {
 }  // namespace smash
 
 extern "C" uint64_t smash_pipeline_key_capacity(const smash_pipeline *p) {
-  // keys the set takes for sure: half its slots, and 16 words of arena each
-  return p ? std::min<uint64_t>((p->table_mask + 1) / 2, p->arena_cap / 16) : 0;
+  // keys the set takes for sure: half its slots, a row each and, for an
+  // owner's set, 16 words of arena each
+  if (!p) return 0;
+  const uint64_t cap = std::min<uint64_t>((p->table_mask + 1) / 2, p->row_cap);
+  return p->owner_arena ? std::min<uint64_t>(cap, p->arena_cap / 16) : cap;
 }
 
 extern "C" int smash_pipeline_map_hints(const smash_pipeline *p) { return p && p->mhint ? 1 : 0; }
@@ -2366,6 +2463,11 @@ extern "C" int smash_pipeline_reset_ex(smash_pipeline *p, uint32_t flags, void *
   SMASH_HIP(hipMemsetAsync(p->d_table, 0, 16 * (p->table_mask + 1), s));
   SMASH_HIP(hipMemsetAsync(p->d_arena_top, 0, 8, s));
   p->keys_bound = 0;
+  // the new run's rows start over.  Its post stages are queued on the
+  // caller's stream behind everything of the previous run that reads the
+  // rows (the search streams never touch them), so stream order keeps a new
+  // row from landing under a reader of the old one.
+  p->row_base = p->row_next = 0;
   SMASH_HIP(hipMemsetAsync(p->d_stats, 0, 8 * kStatWords, s));
   k_reset_prev<<<1, 1, 0, s>>>(p->d_prev);   // no host source: stays asynchronous
   SMASH_HIP(hipGetLastError());
@@ -2508,7 +2610,7 @@ extern "C" int smash_pipeline_positions(smash_pipeline *p, int64_t *h_pos0, int6
   if (p->pos_dirty && p->n_pairs) {   // write the last batch's positions now
     SMASH_HIP(ensure_positions(p));
     k_emit<<<grid_for(p->n_pairs, kB, 1u << 30), kB, 0, p->last>>>(
-        p->d_keep, p->d_nk, hit_rows(p), p->d_posoff, p->n_pairs, p->d_chrom_off,
+        p->d_keep, pair_nk(p), hit_rows(p), p->d_posoff, p->n_pairs, p->d_chrom_off,
         p->d_pos0, p->d_abs);
     SMASH_HIP(hipGetLastError());
     p->pos_dirty = false;
