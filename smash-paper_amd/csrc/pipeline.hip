@@ -227,7 +227,8 @@ struct PostCfg {
   // the search's map hints (SearchWs::mhint): a match word carries its
   // alignment's right map.bin byte before the edge rule, in bits 40..47 if
   // the match is on the forward strand, in bits 33..39 if on the reverse
-  // strand (0: none)
+  // strand (0: none); the other strand's field bounds its left byte
+  // (mate_fast)
   bool mhint;
   // variable-length kernels (VAR): the batch's 2 * n_pairs mate lengths
   // (k_row_lens); L above is then the longest a mate can be
@@ -631,7 +632,7 @@ __device__ __forceinline__ void sort_net(uint64_t (&v)[N]) {
 // directory cells, two contig starts per cell, the contig's start / sizes /
 // tag offset / small flag, and the two map.bin bytes of every alignment.  A
 // slot without a load to make (past n, invalid, or a map byte the search's
-// hint already gave) reads a fixed address instead (c.map: one hot line), so
+// hints already gave or bound) reads a fixed address instead (c.map: one hot line), so
 // no load waits on a branch and the rounds overlap their slots' latencies
 // (each slot was a chain of ~4 dependent loads, one slot after the other).
 // (L: the mate's length, c.L in the fixed-length kernels)
@@ -640,7 +641,7 @@ __device__ __forceinline__ void mate_fast(const PostCfg &c, const uint64_t *__re
                                           const uint64_t *m, uint32_t n, uint64_t (&H)[CAP],
                                           int32_t &err, const uint32_t L) {
   uint64_t A[CAP];
-  uint32_t R[CAP];   // payload through the sort: left byte | right byte << 8 | small << 16
+  uint32_t R[CAP];   // payload through the sort: left byte (or its bound) | right byte << 8 | small << 16
   uint64_t w[CAP];
 #pragma unroll
   for (int k = 0; k < CAP; ++k) w[k] = uint32_t(k) < n ? m[k] : 0;
@@ -699,7 +700,9 @@ __device__ __forceinline__ void mate_fast(const PostCfg &c, const uint64_t *__re
   // m is the chain hint: the shortest unique string ending there, by the
   // text's closure under reverse complement the shortest unique one starting
   // at the base; m + i >= S is m >= o + len
-  // (xl / xr: the bytes' map entries minus 2, halved; 0 = none to load)
+  // (xl / xr: the bytes' map entries minus 2, halved; 0 = none to load;
+  // hint: the right byte in bits 0..7 when bit 8 says it is given, the left
+  // byte's bound + 1 in bits 16..23 when it stands for the byte, else 0)
   uint32_t hint[CAP], xl[CAP], xr[CAP];
 #pragma unroll
   for (int k = 0; k < CAP; ++k) {
@@ -715,18 +718,40 @@ __device__ __forceinline__ void mate_fast(const PostCfg &c, const uint64_t *__re
     A[k] = ok ? (uint64_t(rc) << 63) | (uint64_t(si >> 1) << 48) | (uint64_t(pos) << 16) |
                     (prefix << 8) | len
               : ~0ull;
+    // (a kept slot's offset o and its contig's size S are below 2^31: the
+    // host's check of the contigs)
+    const uint32_t o = uint32_t(ref - spi[k]), S = uint32_t(sz[k]);
+    const uint32_t hs = !c.mhint ? 0u : uint32_t(w[k] >> 40) & 0xFFu;
+    const uint32_t hc = !c.mhint ? 0u : uint32_t(w[k] >> kPkPosBits) & 0x7Fu;
     // (a reverse-strand match that runs past its contig's end has no mirror
     // in the forward contig: no hint, the byte is loaded as before)
-    const uint64_t o = ref - spi[k];
-    const uint32_t h = !c.mhint ? 0u : !rc ? uint32_t(w[k] >> 40) & 0xFFu
-                       : o + len <= sz[k] ? uint32_t(w[k] >> kPkPosBits) & 0x7Fu : 0u;
-    const bool edge = rc ? h >= o + len : o + h >= sz[k];
+    const uint32_t h = !rc ? hs : o + len <= S ? hc : 0u;
+    const bool edge = rc ? h >= o + len : o + h >= S;
     hint[k] = h ? 0x100u | (edge ? 0u : h) : 0u;
     // (mapb: an entry past the map reads 0)
     const uint32_t abspos = toff[k] + uint32_t(pos) + 1;
     const uint32_t bl = abspos + uint32_t(prefix) + len - 1, br = abspos + uint32_t(prefix) - 1;
-    xl[k] = ok && 2 + uint64_t(bl) * 2 < c.map_bytes ? bl + 1 : 0u;
-    xr[k] = ok && !hint[k] && 2 + uint64_t(br) * 2 + 1 < c.map_bytes ? br + 1 : 0u;
+    // The left byte sits at e, the forward base after the block's end (offset
+    // ie in its contig), and is m of e's mirror, zeroed when m >= ie
+    // (longSA.cpp:667).  Only left = byte - 1 against the block's length and
+    // the filter below read it, and a string that holds a unique string is
+    // unique, m(x - 1) <= m(x) + 1: a hint that is m of the mirror's right
+    // neighbour bounds the byte by ub + 1.  Forward match: the neighbour
+    // mirrors the match's last base, the chain hint; reverse-strand match: it
+    // is the match's first base, its SA row's hint.  With e inside the contig
+    // and ub + 1 < ie the byte is in [1, ub + 1]; with ub <= len and ub <=
+    // len - min_excess the bound in the byte's place changes neither the
+    // error check nor any group's filter (a group spans at least its first
+    // block's length): the byte is not loaded
+    const uint32_t ub = rc ? hs : hc;
+    const uint32_t ie = rc ? S - o : o + len;
+    const bool inside = rc ? o >= 1 && o + len <= S : o + len < S;
+    const bool bound = ub != 0 && inside && ub + 1 < ie && ub <= len &&
+                       c.min_excess <= int32_t(len - ub);
+    const bool lmap = ok && 2 + uint64_t(bl) * 2 < c.map_bytes;
+    xl[k] = lmap && !bound ? bl + 1 : 0u;
+    hint[k] |= lmap && bound ? (ub + 1) << 16 : 0u;
+    xr[k] = ok && !(hint[k] & 0x100u) && 2 + uint64_t(br) * 2 + 1 < c.map_bytes ? br + 1 : 0u;
   }
   // round 5: every map byte at once (entry 2 + 2 b (+ 1), b = x - 1; x = 0
   // reads the map's first byte, a hot line, and is dropped)
@@ -735,7 +760,7 @@ __device__ __forceinline__ void mate_fast(const PostCfg &c, const uint64_t *__re
     const uint32_t lb = c.map[xl[k] ? uint64_t(xl[k]) * 2 : 0];
     const uint32_t rb = c.map[xr[k] ? uint64_t(xr[k]) * 2 + 1 : 0];
     const bool ok = A[k] != ~0ull;
-    const uint32_t lm = xl[k] ? lb : 0u;
+    const uint32_t lm = xl[k] ? lb : hint[k] >> 16;   // (the left byte's bound, or 0)
     const uint32_t rm = !ok ? 0u : (hint[k] & 0x100u) ? (hint[k] & 0xFFu) : xr[k] ? rb : 0u;
     R[k] = lm | (rm << 8) | (((sml >> k) & 1u) << 16);
   }
@@ -778,8 +803,10 @@ __device__ __forceinline__ bool hit_kept(uint64_t h) { return h != ~0ull && ((h 
 // goes to the `up` list, for k_post_fast<16> or, past 16, k_post).  Pairs:
 // all n_pairs (list == nullptr) or the *n_list listed ones (grid-stride).
 // VAR: every mate's own length (PostCfg::lens) instead of c.L.
+// (8 words per mate run at three waves per SIMD, 168 VGPRs: the bound keeps
+// the register allocation there, without scratch)
 template <int CAP, bool VAR>
-__global__ __launch_bounds__(kB) void k_post_fast(PostCfg c, const uint64_t *__restrict__ match,
+__global__ __launch_bounds__(kB, CAP <= 8 ? 3 : 1) void k_post_fast(PostCfg c, const uint64_t *__restrict__ match,
                                                   const uint32_t *__restrict__ nmatch,
                                                   uint64_t n_pairs, const uint32_t *list,
                                                   const uint32_t *n_list, uint32_t lim,
