@@ -53,7 +53,7 @@ def _edge_reads(ix, L, n, rng):
     return out
 
 
-@pytest.mark.parametrize("L", [15, 32, 33, 100, 128, 129, 150, 255])
+@pytest.mark.parametrize("L", [15, 32, 33, 40, 41, 100, 128, 129, 137, 150, 153, 255])
 @pytest.mark.parametrize("direct", ["1", "0"])
 def test_state_machine_edge_reads(emu, tiny_ix, L, direct, monkeypatch):
     """bytes absent from the text, 'n' (present), windows at the read end,
@@ -67,8 +67,14 @@ def test_state_machine_edge_reads(emu, tiny_ix, L, direct, monkeypatch):
     reads = np.concatenate([reads, np.array([np.frombuffer(x, np.uint8) for x in extra])])
     for e in (emu[0], emu[2]):
         # (tiny index: K 9, B 11, so min_len 22 / 24 put the filter's window
-        # spread D at 11 / 13, where its second entry no longer fits fk)
-        for ml, lin in ((20, 2), (12, 2), (30, 2), (20, 1), (12, 1), (22, 2), (24, 2)):
+        # spread D at 11 / 13, where its second entry no longer fits fk; 10:
+        # below B, no filter; 11 / 13: D 0 / 2; 25: D + 3 = 17, no filter;
+        # 40 | 41, 137, 153: the LDS row's steps, tests/geometry_inputs.py)
+        B = tiny_ix.acc.B
+        assert B == 11
+        mls = [(20, 2), (12, 2), (30, 2), (20, 1), (12, 1), (22, 2), (24, 2),
+               (B - 1, 2), (B, 2), (B + 2, 2), (B + 14, 2)] + ([(2, 2)] if L == 32 else [])
+        for ml, lin in mls:
             got, _ = e.map(reads, min_len=ml, lin_blocks=lin)
             for i in range(len(reads)):
                 assert got[i] == tiny_ix.search(reads[i].tobytes(), min_len=ml), (e.packed, ml, lin, i)
