@@ -112,6 +112,24 @@ __device__ __forceinline__ uint4 load16u(const uint8_t *p) {
   __builtin_memcpy(&v, p, 16);
   return v;
 }
+// the block U[xr - 15 .. xr] of the reverse-complement position xr = top - ib
+// of a thread's first base ib (top = sp + 2 S).  In the text's first contig
+// the block can begin before U: when xr < 15 (the bytes before U read
+// 0xFF, the others are loaded one by one), and for
+// a thread whose bases lie past a contig shorter than half a tile (ib > top:
+// no base of its own, nothing is loaded)
+__device__ __forceinline__ uint4 load16u_rc(const uint8_t *U, uint64_t top, uint64_t ib) {
+  uint32_t w[4] = {~0u, ~0u, ~0u, ~0u};
+  if (ib <= top) {
+    const uint64_t xr = top - ib;
+    if (xr >= 15) return load16u(U + xr - 15);
+    for (uint32_t j = 15 - uint32_t(xr); j < 16; ++j) {
+      const uint32_t sh = 8 * (j & 3);
+      w[j >> 2] = (w[j >> 2] & ~(0xFFu << sh)) | (uint32_t(U[xr + j - 15]) << sh);
+    }
+  }
+  return make_uint4(w[0], w[1], w[2], w[3]);
+}
 __device__ __forceinline__ uint32_t byte_of(const uint4 &v, uint32_t q) {
   const uint32_t w = q < 4 ? v.x : q < 8 ? v.y : q < 12 ? v.z : v.w;
   return (w >> (8 * (q & 3))) & 0xFF;
@@ -344,9 +362,9 @@ __global__ __launch_bounds__(kMB, W) void k_mapscan(MapCtx c, const IdxT *__rest
                : INT64_MAX;
     if (!PF_U) return x;
     const uint64_t ib = g.i0 + (T - g.tile0) * kTile + uint64_t(threadIdx.x) * kMPer;
-    const uint64_t xf = g.sp + ib, xr = g.sp + 2 * g.S - ib;
+    const uint64_t xf = g.sp + ib;
     x.fw = xf + 16 <= N + 64 ? load16u(U + xf) : make_uint4(~0u, ~0u, ~0u, ~0u);
-    x.rw = xr >= 15 ? load16u(U + xr - 15) : make_uint4(~0u, ~0u, ~0u, ~0u);
+    x.rw = load16u_rc(U, g.sp + 2 * g.S, ib);
     return x;
   };
   uint32_t par = 0;
@@ -368,8 +386,11 @@ __global__ __launch_bounds__(kMB, W) void k_mapscan(MapCtx c, const IdxT *__rest
     unsigned long long mine = 0;
     uint32_t d = 0;   // bin ordinal offset from o0 (monotone over the thread's bases)
     for (uint32_t r = 0; r < uint32_t(SUB); ++r) {
-    // (block-uniform: a sub-tile past the segment's end is skipped whole, so
-    // a thread's rc position xr never falls below the contig's own text)
+    // (block-uniform: a sub-tile past the segment's end is skipped whole.
+    // Within a sub-tile a thread whose bases lie past the end of a short
+    // first contig has ib > sp + 2 S: its xr below wraps, load16u_rc loads
+    // nothing for it, every bit of its satr is set and its fr is kNone; it
+    // has no base of its own, so no xr - q of it is ever an address)
     if (r && t0 + r * kMTile >= i1) break;
     // this thread's 16 bases: U at the forward positions (ascending) and at
     // the reverse-complement positions (descending; byte 15 - q is base q)
@@ -378,7 +399,7 @@ __global__ __launch_bounds__(kMB, W) void k_mapscan(MapCtx c, const IdxT *__rest
     uint4 fw = cur.fw, rw = cur.rw;
     if (!PF_U) {
       fw = xf + 16 <= N + 64 ? load16u(U + xf) : make_uint4(~0u, ~0u, ~0u, ~0u);
-      rw = xr >= 15 ? load16u(U + xr - 15) : make_uint4(~0u, ~0u, ~0u, ~0u);
+      rw = load16u_rc(U, sp + 2 * S, ib);
     }
     // bit q: U == 255 at base ib + q (or past the text), 4 bytes per step:
     // a byte is 0xFF iff its complement is zero
