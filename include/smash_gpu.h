@@ -501,6 +501,35 @@ typedef struct {
 /* Synchronises the pipeline's last stream. */
 int smash_pipeline_stats(smash_pipeline *p, smash_stats *out);
 
+/* ---- many samples in one run ---------------------------------------------- */
+/* A run may hold several samples, as a demultiplexed lane does: sample s is
+ * the run's pairs [h_first[s], h_first[s + 1]), counted from the last reset
+ * across batches; h_first[0 .. n_samples] ascending, h_first[0] = 0.  A
+ * boundary may fall anywhere in a batch, a sample may be empty or span many
+ * batches.  Each sample is counted exactly as a run of its own pairs alone:
+ * the pair de-dup is first-wins within the sample (equal keys of two samples
+ * are both kept), the adjacent de-dup starts with no previous line at the
+ * sample's first pair, its counts go to row s of d_counts, which
+ * smash_count_batch, smash_count_batches and smash_count_batches_ready then
+ * take as [n_samples][nbins], and its statistics are kept apart
+ * (smash_pipeline_sample_stats).  The table stays set across resets.
+ * n_samples = 0: back to the plain run.
+ * Legal right after a reset or before a run's first batch.  SMASH_ERR_ARG: a
+ * table that is not ascending or does not start at 0, n_samples > 65535, a
+ * run under way.  Synchronous (it waits for the device).  With a table set a
+ * batch that would take the run past h_first[n_samples] is SMASH_ERR_ARG when
+ * it is queued, and the multi-GPU phase calls and smash_count_fastq return
+ * SMASH_ERR_UNSUPPORTED.  Variable-length mode works as without a table. */
+int smash_pipeline_samples(smash_pipeline *p, const uint64_t *h_first, uint32_t n_samples);
+typedef struct {
+  uint64_t pairs, key_pairs, dupe_pairs, positions, dups, kept;   /* as smash_stats */
+} smash_sample_stats;
+/* The counters of the first min(cap, n_samples) samples so far, each what
+ * smash_pipeline_stats reports for a run of that sample's pairs alone
+ * (matches and error stay run-wide: smash_pipeline_stats, whose other
+ * counters are the sums over the samples).  Synchronises. */
+int smash_pipeline_sample_stats(smash_pipeline *p, smash_sample_stats *out, uint32_t cap);
+
 /* Kernel timing for the roofline: when enabled, HIP events are recorded on
  * the launch stream around the search kernel (k_mam) of every phase_map /
  * count_batch; _read synchronises and returns the summed milliseconds, the

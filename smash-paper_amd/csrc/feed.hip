@@ -38,6 +38,7 @@ namespace smash {
 uint32_t pipe_read_len(const smash_pipeline *p);
 uint32_t pipe_stride(const smash_pipeline *p);
 bool pipe_var_len(const smash_pipeline *p);
+bool pipe_samples(const smash_pipeline *p);
 uint64_t pipe_max_pairs(const smash_pipeline *p);
 int pipe_device(const smash_pipeline *p);
 void *&pipe_feed(smash_pipeline *p, void (*freer)(void *));
@@ -736,6 +737,10 @@ extern "C" int smash_count_fastq(smash_pipeline *p, const char *const *r1, uint3
   if (!p || !r1 || !r2 || n1 == 0 || n2 == 0 || !d_counts) {
     smash::set_error("smash_count_fastq: bad arguments");
     return SMASH_ERR_ARG;
+  }
+  if (smash::pipe_samples(p)) {   // (file-overlapped multi-sample runs: not built)
+    smash::set_error("smash_count_fastq: not supported while a sample table is set");
+    return SMASH_ERR_UNSUPPORTED;
   }
   const auto t_start = Clock::now();
   auto f = std::make_unique<Feed>();

@@ -35,6 +35,14 @@ namespace {
 // kernel boundary, and against this launch's claims through the claimers' own
 // input rows (the claim / decide kernels below).  Epochs run from 1 and wrap
 // after 2^24 launches; a row ref's epoch field is 0.
+//
+// With a sample table set (smash_pipeline_samples) a key is the hit list AND
+// the sample of its pair: the sample-aware claim / decide (SamplePairKeys)
+// salt the hash hi the table sees with the sample, so equal hit lists of two
+// samples start two probe chains, and compare the sample exactly wherever
+// they compare the words: a row record's is that of its pair g (a bisect
+// over the table, SampleTab::of), an arena record keeps sample + 1 in the high
+// half of its nk word (0 there: a record of a run without a table).
 constexpr int kRefShift = 40;
 // a published arena ref carries kRefPub; row refs and claims do not
 constexpr uint64_t kRefPub = 1ull << 39;
@@ -54,6 +62,15 @@ struct KeyRef {
 
 __device__ bool same_key(const uint64_t *rec, const KeyRef &k) {
   if (rec[0] != k.lo || rec[1] != k.nk) return false;
+  for (uint32_t i = 0; i < k.nk; ++i)
+    if (rec[2 + i] != k.w[i]) return false;
+  return true;
+}
+
+// against an arena record of a run with a sample table: the nk word's high
+// half is the record's sample + 1
+__device__ bool same_key(const uint64_t *rec, const KeyRef &k, uint32_t smp) {
+  if (rec[0] != k.lo || rec[1] != (uint64_t(smp + 1) << 32 | k.nk)) return false;
   for (uint32_t i = 0; i < k.nk; ++i)
     if (rec[2 + i] != k.w[i]) return false;
   return true;
@@ -141,10 +158,12 @@ constexpr uint32_t kDecGroups = 4;
 // incl(l) > t and consecutive lanes store consecutive words (a lane-per-record
 // loop stores 64 words a record apart per instruction).  ok: the lane's
 // record fits the arena; lo / m / src: its hash lo, word count and words.
-// Every lane of the wave calls it (wave-uniform trip count).
+// Every lane of the wave calls it (wave-uniform trip count).  SMP: the nk word
+// carries smp + 1 in its high half (the key's sample).
+template <bool SMP>
 __device__ __forceinline__ void wave_fill_records(uint64_t *arena, uint64_t off, uint32_t incl,
                                                   uint32_t total, bool ok, uint64_t lo, uint32_t m,
-                                                  const uint64_t *src) {
+                                                  const uint64_t *src, uint32_t smp) {
   const uint32_t lane = threadIdx.x & 63;
   const uint64_t srcv = reinterpret_cast<uint64_t>(src);
   for (uint32_t t0 = 0; t0 < total; t0 += 64) {
@@ -156,7 +175,12 @@ __device__ __forceinline__ void wave_fill_records(uint64_t *arena, uint64_t off,
     const uint64_t loff = __shfl(off, int(l), 64), llo = __shfl(lo, int(l), 64);
     const uint32_t lm = uint32_t(__shfl(int(m), int(l), 64));
     const uint64_t *ls = reinterpret_cast<const uint64_t *>(__shfl(srcv, int(l), 64));
-    if (t < total && lok) arena[loff + r] = r == 0 ? llo : r == 1 ? uint64_t(lm) : ls[r - 2];
+    if constexpr (SMP) {
+      const uint64_t nkw = uint64_t(uint32_t(__shfl(int(smp), int(l), 64)) + 1) << 32 | lm;
+      if (t < total && lok) arena[loff + r] = r == 0 ? llo : r == 1 ? nkw : ls[r - 2];
+    } else {
+      if (t < total && lok) arena[loff + r] = r == 0 ? llo : r == 1 ? uint64_t(lm) : ls[r - 2];
+    }
   }
 }
 
@@ -214,12 +238,12 @@ constexpr uint64_t kSlotIns = 1ull << 62;
 // and claimed(ref, epoch, j2) whether a ref is a claim of this launch, and
 // whose; kMarks: its claims mark the slots they fill and the claims they
 // lower (kSlotIns / contest); in_arena(m): a kept key of m words needs an
-// arena record.
+// arena record; kSamples: the key includes the sample of its pair, sample(j).
 //
 // the batch's pairs (single GPU): k_post's nk / hash / hit rows, which start
 // at pair row_base of the run's
 struct PairKeys {
-  static constexpr bool kMarks = true;
+  static constexpr bool kMarks = true, kSamples = false;
   const int32_t *nk;
   const uint64_t *hash;
   HitRows hits;
@@ -239,6 +263,24 @@ struct PairKeys {
     const int32_t k = nk[q];
     return KeyRef{hits.row(q, k), uint32_t(k), hash[2 * q + 1]};
   }
+  __device__ __forceinline__ uint32_t sample(uint64_t) const { return 0; }
+};
+
+// the batch's pairs of a run with a sample table: PairKeys whose key includes
+// the pair's sample.  The hash hi is salted with it (hmask: the post stage's
+// hash mask, kept by the salted value too); lo stays the words' own, the
+// sample is compared exactly beside it
+struct SamplePairKeys : PairKeys {
+  static constexpr bool kSamples = true;
+  SampleTab tab;
+  uint64_t hmask;
+  __device__ __forceinline__ uint32_t sample(uint64_t q) const { return tab.of(row_base + q); }
+  __device__ __forceinline__ KeyRef key(uint64_t q, uint64_t *hi = nullptr) const {
+    if (hi)
+      *hi = (mix64(hash[2 * q] + (uint64_t(sample(q)) + 1) * 0x9E3779B97F4A7C15ull) & hmask) | 1;
+    const int32_t k = nk[q];
+    return KeyRef{hits.row(q, k), uint32_t(k), hash[2 * q + 1]};
+  }
 };
 
 // an owner's received keys: header j = nk << 40 | word offset in its source
@@ -246,7 +288,7 @@ struct PairKeys {
 // base[65..65+world]: word prefix per source rank.  The hashes do not travel:
 // they are recomputed from the words
 struct RecvKeys {
-  static constexpr bool kMarks = false;
+  static constexpr bool kMarks = false, kSamples = false;
   const uint64_t *recv, *words, *base;
   int world;
   uint64_t hmask;
@@ -272,6 +314,7 @@ struct RecvKeys {
     if (hi) *hi = h;
     return k;
   }
+  __device__ __forceinline__ uint32_t sample(uint64_t) const { return 0; }
 };
 
 // The claim of key j (see above): its slot_of value.  err: the first error
@@ -284,6 +327,8 @@ __device__ __forceinline__ uint64_t claim_key(const Src &src, uint64_t j, const 
   uint64_t hi = 0;
   const KeyRef me = src.key(j, &hi);
   const unsigned long long mine = src.claim(j, epoch);
+  uint32_t smp = 0;   // (kSamples) the sample every equal key must share
+  if constexpr (Src::kSamples) smp = src.sample(j);
   uint64_t res = kSlotNone;
   uint64_t i = key_home(hi, mask);
   uint32_t waits = 0;
@@ -314,7 +359,29 @@ __device__ __forceinline__ uint64_t claim_key(const Src &src, uint64_t j, const 
         continue;
       }
       uint64_t j2 = 0;
-      if (ref & kRefPub) {
+      if constexpr (Src::kSamples) {
+        // the plain comparisons below, and the samples must agree: an arena
+        // record's, a claim's pair's and a row's pair's (SamplePairKeys)
+        if (ref & kRefPub) {
+          if ((ref >> kRefShift) != epoch &&
+              same_key(st.arena + ((ref & (kRefPub - 1)) - 1), me, smp)) {
+            res = kSlotOld;
+            break;
+          }
+        } else if (src.claimed(ref, epoch, j2)) {
+          if (src.sample(j2) == smp && same_key(me, src.key(j2))) {
+            src.contest[j2] = 1;
+            atomicMin(sr, mine);
+            res = i;
+            break;
+          }
+        } else if ((ref >> kRefShift) == 0) {
+          if (src.tab.of(ref - 1) == smp && same_key(st, ref - 1, me)) {
+            res = kSlotOld;
+            break;
+          }
+        }
+      } else if (ref & kRefPub) {
         if ((ref >> kRefShift) != epoch &&
             same_key(st.arena + ((ref & (kRefPub - 1)) - 1), me)) {
           res = kSlotOld;
@@ -407,7 +474,9 @@ __device__ __forceinline__ bool decide_keys(const Src &src, uint64_t n, uint64_t
         const bool ok = need && off + need <= arena_cap;
         KeyRef me{nullptr, 0u, 0ull};
         if (need) me = src.key(j);
-        wave_fill_records(arena, off, incl, total, ok, me.lo, me.nk, me.w);
+        uint32_t smp = 0;
+        if constexpr (Src::kSamples) smp = need ? src.sample(j) : 0u;
+        wave_fill_records<Src::kSamples>(arena, off, incl, total, ok, me.lo, me.nk, me.w, smp);
         if (need) {
           if (!ok) {
             full = true;   // the slot stays a claim: never matched (no kRefPub)
@@ -429,6 +498,8 @@ __device__ __forceinline__ bool decide_keys(const Src &src, uint64_t n, uint64_t
   return full;
 }
 
+// (k_dedup_claim_smp / k_dedup_decide_smp below: the same two kernels over
+// SamplePairKeys, launched when a sample table is set)
 __global__ void k_dedup_claim(const int32_t *__restrict__ nk, const uint64_t *__restrict__ hash,
                               HitRows hits, uint64_t n, uint64_t row_base, KeyStore st,
                               uint64_t epoch, uint64_t *slot_of, uint8_t *contest,
@@ -466,6 +537,50 @@ __global__ void k_dedup_decide(const int32_t *__restrict__ nk, const uint64_t *_
         }
         keep[q] = win ? 1 : 0;
         cnt[q] = win ? nmajor[q] : 0;   // k_count_last
+      });
+  wave_stats(stats, S_KEYPAIRS, kp, S_DUPEPAIRS, dp, full ? SMASH_ERR_NOMEM : 0);
+}
+
+__global__ void k_dedup_claim_smp(const int32_t *__restrict__ nk,
+                                  const uint64_t *__restrict__ hash, HitRows hits, uint64_t n,
+                                  uint64_t row_base, KeyStore st, uint64_t epoch,
+                                  uint64_t *slot_of, uint8_t *contest, unsigned long long *stats,
+                                  SampleTab tab, uint64_t hmask) {
+  SMASH_BESIDE_SEARCH();
+  const SamplePairKeys src{{nk, hash, hits, contest, row_base}, tab, hmask};
+  const uint64_t stride = uint64_t(gridDim.x) * blockDim.x;
+  int32_t err = 0;
+  for (uint64_t q = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; q < n; q += stride)
+    if (nk[q] >= 0) slot_of[q] = claim_key(src, q, st, epoch, err);
+  if (err) atomicCAS(&stats[S_ERR], 0ull, (unsigned long long)(unsigned)err);
+}
+
+// (the per-sample key and duplicate counts are taken by the sample-aware emit
+// kernel, which walks the pairs sample by sample; the run's totals here)
+__global__ void k_dedup_decide_smp(const int32_t *__restrict__ nk,
+                                   const uint64_t *__restrict__ hash, HitRows hits,
+                                   const uint32_t *__restrict__ nmajor, uint64_t n,
+                                   uint64_t row_base, uint64_t *table, uint64_t *arena,
+                                   uint64_t arena_cap, unsigned long long *arena_top,
+                                   uint64_t epoch, const uint64_t *__restrict__ slot_of,
+                                   const uint8_t *__restrict__ contest, uint8_t *keep,
+                                   uint32_t *cnt, int64_t *lp, unsigned long long *stats,
+                                   SampleTab tab, uint64_t hmask) {
+  SMASH_BESIDE_SEARCH();
+  const SamplePairKeys src{{nk, hash, hits, const_cast<uint8_t *>(contest), row_base}, tab, hmask};
+  unsigned long long kp = 0, dp = 0;
+  const bool full = decide_keys(
+      src, n, table, arena, arena_cap, arena_top, epoch, slot_of,
+      [&](uint64_t q, bool win) __attribute__((always_inline)) {
+        if (nk[q] >= 0) {
+          ++kp;
+          if (!win) {
+            ++dp;
+            lp[q] = -1;
+          }
+        }
+        keep[q] = win ? 1 : 0;
+        cnt[q] = win ? nmajor[q] : 0;
       });
   wave_stats(stats, S_KEYPAIRS, kp, S_DUPEPAIRS, dp, full ? SMASH_ERR_NOMEM : 0);
 }

@@ -168,6 +168,12 @@ struct smash_pipeline {
                                   // before the set's next search)
   bool pos_dirty = false;         // the positions arrays are not materialised yet
   unsigned long long *d_stats = nullptr;
+  // the sample table (smash_pipeline_samples; empty: a plain run): its host
+  // image, the device's [n + 1] and the per-sample counters [n][SS_N]
+  std::vector<uint64_t> h_first;
+  uint64_t *d_first = nullptr;
+  unsigned long long *d_sstats = nullptr;
+  uint32_t bin_short = 0;         // the sample-aware emit kernel's short-run threshold (pairs)
   uint32_t *d_fb = nullptr;       // [1 + max_pairs]: k_post_fast<16> -> k_post pair list
   uint32_t *d_l16 = nullptr;      // [1 + max_pairs]: k_post_fast<8> -> k_post_fast<16>
   uint8_t *d_post_ws = nullptr;   // k_post workspace: kPostThreads slices
@@ -253,6 +259,27 @@ struct HitRows {
     return nk <= int32_t(kHitHead) ? head + q * kHitHead : full + q * 2 * uint64_t(slots);
   }
 };
+
+// The run's sample table (smash_pipeline_samples): sample s is the run's
+// pairs [first[s], first[s + 1]), first[0] = 0, ascending; n samples.  The
+// sample of a pair follows from its index in the run alone.
+struct SampleTab {
+  const uint64_t *first;   // [n + 1]
+  uint32_t n;
+  // the sample of the run's pair g < first[n]: the last s with first[s] <= g
+  // (the samples before it that start at the same pair are empty)
+  __device__ __forceinline__ uint32_t of(uint64_t g) const {
+    uint32_t lo = 0, hi = n;   // upper_bound(first[0..n), g) - 1
+    while (lo < hi) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if (first[mid] <= g) lo = mid + 1; else hi = mid;
+    }
+    return lo - 1;
+  }
+};
+// per-sample counters, d_sstats[sample][SS_N] (the pairs are the host's: the
+// table and the run's pair count give them)
+enum SampleStat { SS_KEYPAIRS, SS_DUPEPAIRS, SS_POS, SS_DUPS, SS_KEPT, SS_N };
 
 struct Aln {
   int64_t pos, qpos;
@@ -1230,6 +1257,14 @@ __global__ __launch_bounds__(kB) void k_emit_bin(
 constexpr uint32_t kBinPart = 77824;   // 16-bit counters: 152 KB, one 1024-thread block per CU
 constexpr uint32_t kBinPartsMax = 4;   // above: k_emit_bin
 constexpr uint32_t kBinBlocks = 256;   // k_emit_bin_lds blocks per part (one per CU)
+// k_emit_bin_smp: a sample's run of fewer pairs inside a block's range (less
+// than one trip of the block) goes straight to global atomics.  Measured on
+// one batch cut into samples of r pairs, every run in LDS against every run
+// direct, kernel time from a trace ("Many samples in one
+// run"; profiles/samples1): r = 64: 1.40 vs 0.53 ms, 256: 0.475 vs 0.419,
+// 1024: 0.387 vs 0.377 (1 M pairs) and 2.68 vs 2.66 (8 M), 2048: 0.341 vs 0.363
+// and 2.28 vs 2.61, 4096: 0.305 vs 0.337 and 1.90 vs 2.56
+constexpr uint32_t kBinShortRun = 1024;
 // the parts balanced: ceil(nbins / parts) bins each (50 k bins: 2 x 25 000,
 // not 24 576 + 24 576 + 848 -- every part re-walks all the pairs)
 inline uint32_t bin_parts(uint32_t nbins) { return (nbins + kBinPart - 1) / kBinPart; }
@@ -1337,6 +1372,187 @@ __global__ void k_bin_reduce(const uint32_t *__restrict__ binpart, uint32_t bloc
     for (uint32_t k = 0; k < blocks; ++k) t += binpart[uint64_t(k) * nbins + b];
     if (t) atomicAdd(&counts[b], t);
   }
+}
+
+// ---------------------------------------------------------------------------
+// The sample-aware emit + bin (a sample table is set, SampleTab): the run's
+// pairs are cut into contiguous samples, each with its own adjacent-dup chain,
+// count row counts[s * nbins ...] and counters sstats[s][SS_N].
+//
+// The chain is cut without a scan of its own.  With f the first pair of q's
+// sample in the batch, lps[q - 1] (the last position of the nearest earlier
+// emitting pair) belongs to q's sample iff posoff[q] > posoff[f]: a pair of
+// [f, q) emitted (posoff[q] = the positions emitted before pair q).  The
+// carried line applies only where the sample began in an earlier batch and
+// has emitted nothing in this one.
+//
+// Every block walks a contiguous range of pairs (k_emit_bin_lds's grid stride
+// would mix samples in a block's LDS counters), 1024 consecutive pairs per
+// trip, as maximal runs of one sample.  A run of at least short_run pairs is
+// summed in the 16-bit LDS halves (the same overflow rule as k_emit_bin_lds)
+// and its non-zero halves are flushed into the sample's row at the run's end,
+// between two block barriers; consecutive shorter runs are walked as one
+// stretch, each thread taking its pair's sample from the table, with one
+// global atomic per position.  LDS = false: global atomics only, no LDS
+// (more than kBinPartsMax parts, or SMASH_BIN_LDS=0).  The per-sample
+// counters are reduced per wave, one atomic per counter and sample present in
+// the wave; part 0 keeps them.
+// ---------------------------------------------------------------------------
+// v[k] added to counter k of sample s over the wave's lanes with act, grouped
+// by sample (every lane of the wave calls it)
+__device__ __forceinline__ void wave_sample_stats(unsigned long long *sstats, bool act, uint32_t s,
+                                                  const unsigned long long (&v)[SS_N]) {
+  const uint32_t lane = threadIdx.x & 63;
+  uint64_t todo = __ballot(act);
+  while (todo) {   // (wave-uniform)
+    const int leader = __builtin_ctzll(todo);
+    const uint32_t s0 = uint32_t(__shfl(int(s), leader, 64));
+    const bool in = act && s == s0;
+#pragma unroll
+    for (int k = 0; k < SS_N; ++k) {
+      const unsigned long long t = wave_sum(in ? v[k] : 0ull);
+      if (lane == uint32_t(leader) && t) atomicAdd(&sstats[uint64_t(s0) * SS_N + k], t);
+    }
+    todo &= ~__ballot(in);
+  }
+}
+
+template <bool LDS>
+__global__ __launch_bounds__(1024) void k_emit_bin_smp(
+    const uint8_t *__restrict__ keep, const int32_t *__restrict__ nk, HitRows hits,
+    const int64_t *__restrict__ chrom_off, const int64_t *__restrict__ lps,
+    const uint32_t *__restrict__ posoff, uint64_t n, uint64_t row_base, SampleTab tab,
+    const int64_t *prev_p, const int64_t *__restrict__ bins, uint32_t nbins,
+    const uint32_t *__restrict__ cell, uint32_t ncell, uint32_t cshift, unsigned long long *counts,
+    unsigned long long *stats, unsigned long long *sstats, uint32_t part, uint32_t flush,
+    uint32_t short_run) {
+  __shared__ uint32_t hc[LDS ? kBinPart / 2 : 1];   // bin b0 + i: half i & 1 of word i >> 1
+  const uint32_t b0 = LDS ? blockIdx.y * part : 0u;
+  const uint32_t b1 = LDS ? (b0 + part < nbins ? b0 + part : nbins) : nbins;
+  if constexpr (LDS) {
+    for (uint32_t i = threadIdx.x; i < (part + 1) / 2; i += blockDim.x) hc[i] = 0;
+    __syncthreads();
+  } else {
+    SMASH_BESIDE_SEARCH();
+  }
+  const int64_t prev0 = *prev_p;
+  const bool stat = blockIdx.y == 0;
+  // the block's range: whole trips of blockDim.x consecutive pairs
+  const uint64_t per = ((n + gridDim.x - 1) / gridDim.x + blockDim.x - 1) / blockDim.x * blockDim.x;
+  const uint64_t lo = uint64_t(blockIdx.x) * per;
+  const uint64_t hi = lo + per < n ? lo + per : n;
+  unsigned long long rt = 0, rd = 0, rk = 0;   // the run's totals, this thread's share
+
+  // pair q of sample s, whose first pair in the batch is f (began: the sample
+  // has pairs in earlier batches): its positions into v[SS_POS..SS_KEPT], the
+  // kept ones counted by add(bin)
+  auto walk = [&](uint64_t q, uint64_t f, bool began, unsigned long long (&v)[SS_N], auto add)
+      __attribute__((always_inline)) {
+    const int32_t m0 = nk[q];
+    const bool kp = keep[q] != 0;
+    if (m0 >= 0) {
+      ++v[SS_KEYPAIRS];
+      if (!kp) ++v[SS_DUPEPAIRS];
+    }
+    const int32_t m = kp ? m0 : 0;
+    if (m <= 0) return;
+    int64_t prev = began ? prev0 : -1;
+    if (q > f && posoff[q] > posoff[f]) prev = lps[q - 1];
+    const uint64_t *h = hits.row(q, m0);
+    for (int32_t i = 0; i < m; ++i) {
+      const uint64_t w = h[i];
+      const int64_t co = chrom_off[uint32_t(w >> 48)];
+      if (co < 0) continue;
+      const int64_t p = int64_t(w & 0xFFFFFFFFFFFFull);
+      ++v[SS_POS];
+      if (prev >= 0 && prev == p) {
+        ++v[SS_DUPS];
+      } else {
+        const uint32_t b = bin_of(p + co, bins, nbins, cell, ncell, cshift);
+        if (b >= b0 && b < b1) add(b);
+        ++v[SS_KEPT];
+      }
+      prev = p;
+    }
+  };
+
+  for (uint64_t cur = lo; cur < hi;) {   // (block-uniform)
+    uint32_t s = tab.of(row_base + cur);
+    uint64_t e = tab.first[s + 1] - row_base;   // the end of s's run in the batch
+    e = e < hi ? e : hi;
+    if (LDS && e - cur >= short_run) {
+      const uint64_t fs = tab.first[s];
+      const uint64_t f = fs > row_base ? fs - row_base : 0;
+      unsigned long long *row = counts + uint64_t(s) * nbins;
+      unsigned long long v[SS_N] = {0, 0, 0, 0, 0};
+      for (uint64_t q = cur + threadIdx.x; q < e; q += blockDim.x)
+        walk(q, f, fs < row_base, v, [&](uint32_t b) __attribute__((always_inline)) {
+          const uint32_t sh = 16 * ((b - b0) & 1);
+          const uint32_t old = atomicAdd(&hc[(b - b0) >> 1], 1u << sh);
+          if (((old >> sh) & 0xFFFFu) == flush - 1) {
+            atomicSub(&hc[(b - b0) >> 1], flush << sh);
+            atomicAdd(&row[b], (unsigned long long)flush);
+          }
+        });
+      rt += v[SS_POS];
+      rd += v[SS_DUPS];
+      rk += v[SS_KEPT];
+      wave_sample_stats(sstats, stat, s, v);
+      // the run's counts into its sample's row, the counters cleared for the next run
+      __syncthreads();
+      for (uint32_t i = threadIdx.x; i < (part + 1) / 2; i += blockDim.x) {
+        const uint32_t x = hc[i];
+        if (!x) continue;
+        hc[i] = 0;
+        if (x & 0xFFFFu) atomicAdd(&row[b0 + 2 * i], (unsigned long long)(x & 0xFFFFu));
+        if (x >> 16) atomicAdd(&row[b0 + 2 * i + 1], (unsigned long long)(x >> 16));
+      }
+      __syncthreads();
+      cur = e;
+      continue;
+    }
+    // a stretch of short runs (LDS = false: the rest of the block's range)
+    while (LDS && e < hi) {
+      const uint32_t s2 = tab.of(row_base + e);
+      uint64_t e2 = tab.first[s2 + 1] - row_base;
+      e2 = e2 < hi ? e2 : hi;
+      if (e2 - e >= short_run) break;
+      e = e2;
+    }
+    if (!LDS) e = hi;
+    for (uint64_t q0 = cur; q0 < e; q0 += blockDim.x) {   // (block-uniform trips)
+      const uint64_t q = q0 + threadIdx.x;
+      const bool act = q < e;
+      unsigned long long v[SS_N] = {0, 0, 0, 0, 0};
+      uint32_t sq = 0;
+      if (act) {
+        sq = tab.of(row_base + q);
+        const uint64_t fs = tab.first[sq];
+        unsigned long long *row = counts + uint64_t(sq) * nbins;
+        walk(q, fs > row_base ? fs - row_base : 0, fs < row_base, v,
+             [&](uint32_t b) __attribute__((always_inline)) { atomicAdd(&row[b], 1ull); });
+      }
+      rt += v[SS_POS];
+      rd += v[SS_DUPS];
+      rk += v[SS_KEPT];
+      wave_sample_stats(sstats, act && stat, sq, v);
+    }
+    cur = e;
+  }
+  wave_stats(stats, S_POS, stat ? rt : 0, S_DUPS, stat ? rd : 0, 0);
+  wave_stats(stats, S_KEPT, stat ? rk : 0, S_KEPT, 0, 0);
+}
+
+// the carried line after a batch of a run with a sample table: the last
+// position of the sample that holds the batch's last pair, if it emitted one
+// in this batch; the line carried so far if that sample began in an earlier
+// batch and emitted nothing; else none
+__global__ void k_tail_lps_smp(const uint32_t *posoff, const int64_t *lps, uint64_t n,
+                               uint64_t row_base, SampleTab tab, int64_t *prev) {
+  const uint64_t fs = tab.first[tab.of(row_base + n - 1)];
+  const uint64_t f = fs > row_base ? fs - row_base : 0;
+  if (posoff[n] > posoff[f]) prev[0] = lps[n - 1];
+  else if (fs >= row_base) prev[0] = -1;
 }
 
 // the batch's tail {count, last position} (lps_last: lps[n - 1]; count 0:
@@ -1600,6 +1816,10 @@ extern "C" int smash_pipeline_create(const smash_index *ix,
       const char *fl = getenv("SMASH_BIN_FLUSH");
       const unsigned long f = fl ? std::strtoul(fl, nullptr, 10) : 0;
       if (f >= 2 && f <= 0x8000 && !(f & (f - 1))) p->bin_flush = uint32_t(f);
+      // SMASH_BIN_SHORT (tests, A/B): k_emit_bin_smp's short-run threshold in pairs
+      p->bin_short = kBinShortRun;
+      if (const char *sr = getenv("SMASH_BIN_SHORT"))
+        if (*sr) p->bin_short = uint32_t(std::strtoul(sr, nullptr, 10));
     }
     // (the positions arrays, 2 x 8 B x every hit slot = 26 GB at 6.25 M
     // pairs, are allocated only when smash_pipeline_positions asks:
@@ -1692,7 +1912,8 @@ extern "C" void smash_pipeline_free(smash_pipeline *p) {
                   (void *)p->d_lp, (void *)p->d_lps, (void *)p->d_binpart,
                   (void *)p->d_send_q, (void *)p->d_owner, (void *)p->d_fb, (void *)p->d_l16,
                   (void *)p->d_post_ws, (void *)p->d_arena, (void *)p->d_arena_top,
-                  (void *)p->d_send_hdr, (void *)p->d_send_words, (void *)p->d_recv_base})
+                  (void *)p->d_send_hdr, (void *)p->d_send_words, (void *)p->d_recv_base,
+                  (void *)p->d_first, (void *)p->d_sstats})
     dfree(q);
   delete p;
 }
@@ -1841,14 +2062,26 @@ static int phase_map_impl(smash_pipeline *p, const uint8_t *d_reads, uint64_t n_
   return SMASH_OK;
 }
 
+// the multi-GPU phase calls and the file feed take no sample table
+static int no_samples(const smash_pipeline *p, const char *what) {
+  if (!p || p->h_first.empty()) return SMASH_OK;
+  set_error(std::string(what) + ": not supported while a sample table is set");
+  return SMASH_ERR_UNSUPPORTED;
+}
+namespace smash {
+bool pipe_samples(const smash_pipeline *p) { return !p->h_first.empty(); }
+}  // namespace smash
+
 extern "C" int smash_phase_map(smash_pipeline *p, const uint8_t *d_reads,
                                uint64_t n_pairs, void *stream) {
+  if (int rc = no_samples(p, "smash_phase_map")) return rc;
   return phase_map_impl(p, d_reads, n_pairs, static_cast<hipStream_t>(stream), nullptr);
 }
 
 extern "C" int smash_phase_map_ahead(smash_pipeline *p, const uint8_t *d_reads,
                                      uint64_t n_pairs, const uint8_t *d_next, uint64_t n_next,
                                      void *stream) {
+  if (int rc = no_samples(p, "smash_phase_map_ahead")) return rc;
   return phase_map_impl(p, d_reads, n_pairs, static_cast<hipStream_t>(stream), nullptr, d_next,
                         n_next);
 }
@@ -1862,6 +2095,7 @@ extern "C" int smash_phase_search_ahead(smash_pipeline *p, const uint8_t *d_read
                                         uint64_t n_pairs, void *stream) {
   int rc = check_pipe(p, n_pairs);
   if (rc) return rc;
+  if ((rc = no_samples(p, "smash_phase_search_ahead"))) return rc;
   if (!n_pairs) return SMASH_OK;
   const int k = p->set;   // the set of the batch smash_phase_map last took
   if (p->searched[k]) {
@@ -1883,6 +2117,10 @@ static KeyStore key_store(const smash_pipeline *p) {
   return KeyStore{p->d_table, p->table_mask, p->d_arena, p->d_hhead, p->d_nk};
 }
 
+static SampleTab sample_tab(const smash_pipeline *p) {
+  return SampleTab{p->d_first, uint32_t(p->h_first.size() - 1)};
+}
+
 // single GPU: the persistent set, first occurrence in pair order
 // (k_dedup_claim, k_dedup_decide), and the positions' per-pair counts
 static int dedup_local(smash_pipeline *p, hipStream_t s) {
@@ -1890,6 +2128,21 @@ static int dedup_local(smash_pipeline *p, hipStream_t s) {
   if (!n) return SMASH_OK;
   const uint64_t epoch = next_epoch(p);
   SMASH_HIP(hipMemsetAsync(p->d_contest, 0, n, s));
+  if (!p->h_first.empty()) {   // the key includes the pair's sample
+    const SampleTab tab = sample_tab(p);
+    k_dedup_claim_smp<<<grid_for(n, kB, 8192), kB, 0, s>>>(
+        pair_nk(p), p->d_hash, hit_rows(p), n, p->row_base, key_store(p), epoch, p->d_slot,
+        p->d_contest, p->d_stats, tab, p->hash_mask);
+    SMASH_HIP(hipGetLastError());
+    k_dedup_decide_smp<<<grid_for((n + kDecGroups - 1) / kDecGroups, kB, 8192), kB, 0, s>>>(
+        pair_nk(p), p->d_hash, hit_rows(p), p->d_nmajor, n, p->row_base, p->d_table, p->d_arena,
+        p->arena_cap, p->d_arena_top, epoch, p->d_slot, p->d_contest, p->d_keep, p->d_cnt,
+        p->d_lp, p->d_stats, tab, p->hash_mask);
+    SMASH_HIP(hipGetLastError());
+    p->cnt_ready = true;
+    p->row_next = p->row_base + n;
+    return SMASH_OK;
+  }
   k_dedup_claim<<<grid_for(n, kB, 8192), kB, 0, s>>>(pair_nk(p), p->d_hash, hit_rows(p), n,
                                                      p->row_base, key_store(p), epoch, p->d_slot,
                                                      p->d_contest, p->d_stats);
@@ -1907,9 +2160,7 @@ static int dedup_local(smash_pipeline *p, hipStream_t s) {
   return SMASH_OK;
 }
 
-extern "C" int smash_phase_positions(smash_pipeline *p, int64_t *d_tail, void *stream) {
-  if (!p) return SMASH_ERR_ARG;
-  hipStream_t s = static_cast<hipStream_t>(stream);
+static int positions_impl(smash_pipeline *p, int64_t *d_tail, hipStream_t s) {
   p->last = s;
   const uint64_t n = p->n_pairs;
   // counts, offsets and each pair's preceding line; the positions
@@ -1934,11 +2185,40 @@ extern "C" int smash_phase_positions(smash_pipeline *p, int64_t *d_tail, void *s
   return SMASH_OK;
 }
 
-extern "C" int smash_phase_bin(smash_pipeline *p, const int64_t *d_prev,
-                               uint64_t *d_counts, void *stream) {
-  if (!p || !d_counts) return SMASH_ERR_ARG;
-  hipStream_t s = static_cast<hipStream_t>(stream);
+extern "C" int smash_phase_positions(smash_pipeline *p, int64_t *d_tail, void *stream) {
+  if (!p) return SMASH_ERR_ARG;
+  if (int rc = no_samples(p, "smash_phase_positions")) return rc;
+  return positions_impl(p, d_tail, static_cast<hipStream_t>(stream));
+}
+
+// the batch's emit + bin with a sample table set: d_counts is [S][nbins], the
+// chain, the rows and the counters per sample (k_emit_bin_smp)
+static int bin_samples(smash_pipeline *p, uint64_t *d_counts, hipStream_t s) {
+  const uint64_t n = p->n_pairs;
+  if (!n) return SMASH_OK;
+  const SampleTab tab = sample_tab(p);
+  unsigned long long *counts = reinterpret_cast<unsigned long long *>(d_counts);
+  if (p->bin_lds) {   // (set only when parts <= kBinPartsMax)
+    const unsigned gx = unsigned(std::min<uint64_t>(kBinBlocks, (n + 1023) / 1024));
+    k_emit_bin_smp<true><<<dim3(gx, bin_parts(p->nbins)), 1024, 0, s>>>(
+        p->d_keep, pair_nk(p), hit_rows(p), p->d_chrom_off, p->d_lps, p->d_posoff, n,
+        p->row_base, tab, p->d_prev, p->d_bins, p->nbins, p->d_cell, p->ncell, p->cshift, counts,
+        p->d_stats, p->d_sstats, bin_part_size(p->nbins), p->bin_flush, p->bin_short);
+  } else {
+    k_emit_bin_smp<false><<<grid_for(n, kB, 8192), kB, 0, s>>>(
+        p->d_keep, pair_nk(p), hit_rows(p), p->d_chrom_off, p->d_lps, p->d_posoff, n,
+        p->row_base, tab, p->d_prev, p->d_bins, p->nbins, p->d_cell, p->ncell, p->cshift, counts,
+        p->d_stats, p->d_sstats, 0, 0, 0);
+  }
+  SMASH_HIP(hipGetLastError());
+  k_tail_lps_smp<<<1, 1, 0, s>>>(p->d_posoff, p->d_lps, n, p->row_base, tab, p->d_prev);
+  SMASH_HIP(hipGetLastError());
+  return SMASH_OK;
+}
+
+static int bin_impl(smash_pipeline *p, const int64_t *d_prev, uint64_t *d_counts, hipStream_t s) {
   p->last = s;
+  if (!p->h_first.empty()) return bin_samples(p, d_counts, s);
   const uint64_t n = p->n_pairs;
   const int64_t *prev = d_prev ? d_prev : p->d_prev;
   const uint32_t parts = bin_parts(p->nbins);
@@ -1964,18 +2244,31 @@ extern "C" int smash_phase_bin(smash_pipeline *p, const int64_t *d_prev,
   return SMASH_OK;
 }
 
+extern "C" int smash_phase_bin(smash_pipeline *p, const int64_t *d_prev,
+                               uint64_t *d_counts, void *stream) {
+  if (!p || !d_counts) return SMASH_ERR_ARG;
+  if (int rc = no_samples(p, "smash_phase_bin")) return rc;
+  return bin_impl(p, d_prev, d_counts, static_cast<hipStream_t>(stream));
+}
+
 namespace smash {
 // one batch, its search after in_ev (null: after everything on s so far)
 int count_batch_ev(smash_pipeline *p, const uint8_t *d_reads, uint64_t n_pairs,
                    uint64_t *d_counts, hipStream_t s, hipEvent_t in_ev) {
+  // (the host knows the run's pairs at this point: nothing is queued for a
+  // batch that would pass the table's end)
+  if (p && !p->h_first.empty() && p->row_next + n_pairs > p->h_first.back()) {
+    set_error("smash_count_batch: the batch takes the run past the sample table's last pair");
+    return SMASH_ERR_ARG;
+  }
   p->defer_free = true;   // recorded below, after the batch's whole post stage
   p->keys_bound += n_pairs;
   int rc = phase_map_impl(p, d_reads, n_pairs, s, in_ev);
   p->defer_free = false;
   if (rc) return rc;
   rc = dedup_local(p, s);
-  if (!rc) rc = smash_phase_positions(p, nullptr, s);
-  if (!rc) rc = smash_phase_bin(p, nullptr, d_counts, s);
+  if (!rc) rc = positions_impl(p, nullptr, s);
+  if (!rc) rc = d_counts ? bin_impl(p, nullptr, d_counts, s) : SMASH_ERR_ARG;
   // on every exit once the search is queued: the set's next search must
   // follow whatever of this batch's post stage was queued on s
   if (n_pairs && hipEventRecord(p->ev_free[p->set], s) != hipSuccess && !rc) {
@@ -2220,6 +2513,7 @@ extern "C" int smash_phase_export(smash_pipeline *p, int world, uint64_t global_
     set_error("smash_phase_export: bad arguments");
     return SMASH_ERR_ARG;
   }
+  if (int rc = no_samples(p, "smash_phase_export")) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   p->last = s;
   const uint64_t n = p->n_pairs;
@@ -2270,6 +2564,7 @@ extern "C" int smash_dedup_owner(smash_pipeline *p, const uint64_t *d_recv, uint
     set_error("smash_dedup_owner: bad arguments");
     return SMASH_ERR_ARG;
   }
+  if (int rc = no_samples(p, "smash_dedup_owner")) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   SMASH_HIP(hipEventSynchronize(p->ev_base));   // (the last upload of the image read it)
   uint64_t *base = p->h_recv_base;
@@ -2317,6 +2612,7 @@ extern "C" int smash_dedup_owner(smash_pipeline *p, const uint64_t *d_recv, uint
 extern "C" int smash_phase_import(smash_pipeline *p, const uint8_t *d_flags_back,
                                   void *stream) {
   if (!p) return SMASH_ERR_ARG;
+  if (int rc = no_samples(p, "smash_phase_import")) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   p->last = s;
   if (p->n_export)
@@ -2360,6 +2656,76 @@ extern "C" int smash_pipeline_stats(smash_pipeline *p, smash_stats *o) {
   o->kept = st[S_KEPT];
   o->matches = st[S_MATCHES];
   o->error = int32_t(st[S_ERR]);
+  return SMASH_OK;
+}
+
+// The sample table of the runs to come (smash_gpu.h): legal while the run has
+// no batch yet.  Synchronous: it waits for the device, since the previous
+// run's queued kernels may still read the table it replaces.
+extern "C" int smash_pipeline_samples(smash_pipeline *p, const uint64_t *h_first,
+                                      uint32_t n_samples) {
+  if (!p || (n_samples && !h_first)) return SMASH_ERR_ARG;
+  if (p->row_next) {
+    set_error("smash_pipeline_samples: a run is under way (set the table at a reset)");
+    return SMASH_ERR_ARG;
+  }
+  if (n_samples > 65535) {
+    set_error("smash_pipeline_samples: more than 65535 samples");
+    return SMASH_ERR_ARG;
+  }
+  if (n_samples && h_first[0] != 0) {
+    set_error("smash_pipeline_samples: first[0] must be 0");
+    return SMASH_ERR_ARG;
+  }
+  for (uint32_t k = 0; k < n_samples; ++k)
+    if (h_first[k + 1] < h_first[k]) {
+      set_error("smash_pipeline_samples: the table is not ascending");
+      return SMASH_ERR_ARG;
+    }
+  SMASH_HIP(hipSetDevice(p->device));
+  SMASH_HIP(hipDeviceSynchronize());
+  uint64_t *f = nullptr;
+  unsigned long long *st = nullptr;
+  if (n_samples) {
+    if (hipMalloc(reinterpret_cast<void **>(&f), 8 * (uint64_t(n_samples) + 1)) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void **>(&st), 8 * SS_N * uint64_t(n_samples)) != hipSuccess) {
+      (void)hipFree(f);
+      set_error("smash_pipeline_samples: out of device memory");
+      return SMASH_ERR_NOMEM;
+    }
+    SMASH_HIP(hipMemcpy(f, h_first, 8 * (uint64_t(n_samples) + 1), hipMemcpyHostToDevice));
+    SMASH_HIP(hipMemset(st, 0, 8 * SS_N * uint64_t(n_samples)));
+  }
+  dfree(p->d_first);
+  dfree(p->d_sstats);
+  p->d_first = f;
+  p->d_sstats = st;
+  if (n_samples) p->h_first.assign(h_first, h_first + n_samples + 1);
+  else p->h_first.clear();
+  return SMASH_OK;
+}
+
+extern "C" int smash_pipeline_sample_stats(smash_pipeline *p, smash_sample_stats *out,
+                                           uint32_t cap) {
+  if (!p || (cap && !out)) return SMASH_ERR_ARG;
+  SMASH_HIP(hipSetDevice(p->device));
+  if (p->last) SMASH_HIP(hipStreamSynchronize(p->last));
+  SMASH_HIP(hipDeviceSynchronize());
+  const uint32_t S = p->h_first.empty() ? 0u : uint32_t(p->h_first.size() - 1);
+  const uint32_t m = std::min(S, cap);
+  if (!m) return SMASH_OK;
+  std::vector<unsigned long long> st(uint64_t(m) * SS_N);
+  SMASH_HIP(hipMemcpy(st.data(), p->d_sstats, 8 * st.size(), hipMemcpyDeviceToHost));
+  for (uint32_t k = 0; k < m; ++k) {
+    const unsigned long long *r = st.data() + uint64_t(k) * SS_N;
+    // the sample's pairs counted so far: the run's first row_next pairs
+    out[k].pairs = std::min(p->row_next, p->h_first[k + 1]) - std::min(p->row_next, p->h_first[k]);
+    out[k].key_pairs = r[SS_KEYPAIRS];
+    out[k].dupe_pairs = r[SS_DUPEPAIRS];
+    out[k].positions = r[SS_POS];
+    out[k].dups = r[SS_DUPS];
+    out[k].kept = r[SS_KEPT];
+  }
   return SMASH_OK;
 }
 
@@ -2496,6 +2862,8 @@ extern "C" int smash_pipeline_reset_ex(smash_pipeline *p, uint32_t flags, void *
   // row from landing under a reader of the old one.
   p->row_base = p->row_next = 0;
   SMASH_HIP(hipMemsetAsync(p->d_stats, 0, 8 * kStatWords, s));
+  if (p->d_sstats)   // (the table itself stays: the new run has the same samples)
+    SMASH_HIP(hipMemsetAsync(p->d_sstats, 0, 8 * SS_N * (p->h_first.size() - 1), s));
   k_reset_prev<<<1, 1, 0, s>>>(p->d_prev);   // no host source: stays asynchronous
   SMASH_HIP(hipGetLastError());
   // a look-ahead search not consumed before the reset is dropped (the next

@@ -15,6 +15,10 @@ subcommand below takes the same inputs and writes the same files:
                                 file: ID.varbin.txt and ID.stats.txt
                                 (map / count --max-read-len N: mates of mixed
                                 lengths up to N, e.g. trimmed reads)
+  count-many MANIFEST BINDIR    count for every sample of a demultiplexed lane in
+                                one run: MANIFEST holds ID<TAB>r1 files<TAB>r2 files
+                                per line; ID.varbin.txt and ID.stats.txt per ID,
+                                as `count ID ...` writes them
   memsam [-nomap] [--tag] QUERY.sam
                                 `mummer -rcref -samin -samout [-nomap]`: the
                                 mapout SAM file; --tag adds mappability_tag's
@@ -551,6 +555,89 @@ def cmd_count(args):
                  args.out or args.id + ".varbin.txt", args.id + ".stats.txt")
 
 
+def read_manifest(path):
+    """count-many's MANIFEST: one sample per line, ID<TAB>r1 files<TAB>r2 files
+    (the file lists space-separated, as count takes them); blank lines are
+    skipped.  -> [(id, [r1 paths], [r2 paths])]"""
+    out, seen = [], set()
+    with open(path) as f:
+        for ln, line in enumerate(f, 1):
+            line = line.rstrip("\r\n")
+            if not line.strip():
+                continue
+            cols = [c.strip() for c in line.split("\t")]
+            if len(cols) != 3 or not all(cols):
+                raise SystemExit("%s:%d: expected ID<TAB>r1 files<TAB>r2 files" % (path, ln))
+            if cols[0] in seen:
+                raise SystemExit("%s:%d: sample ID %r is listed twice" % (path, ln, cols[0]))
+            seen.add(cols[0])
+            out.append((cols[0], cols[1].split(), cols[2].split()))
+    if not out:
+        raise SystemExit("%s: no samples" % path)
+    if len(out) > 65535:
+        raise SystemExit("%s: more than 65535 samples" % path)
+    return out
+
+
+def cmd_count_many(args):
+    """every sample of the manifest in one run (smash_pipeline_samples): the
+    samples' pairs, each name-ordered, are packed one after the other into
+    batches, counted with one sample table, and written per ID"""
+    import torch
+    samples = read_manifest(args.manifest)
+    ref = _ref(args)
+    ix = load_index(ref, args.device, _verify_flags(args))
+    cs = S.read_chrom_sizes(args.chrom_sizes or ref + ".bin/chrom_sizes.txt")
+    rows, starts = S.read_bins(os.path.join(args.bindir, "bins.txt"))
+    M = _max_read_len(args)
+    L = M or S.first_read_length(samples[0][1])
+    fqs = []
+    for sid, r1, r2 in samples:
+        try:
+            fqs.append(S.FastqIndex(r1, r2, read_len=(S.SMASH_LEN_VAR | M) if M else L,
+                                    sort_names=not args.presorted))
+        except S.SmashError as e:
+            raise SystemExit("%s: %s" % (sid, _name_option(e, M))) from None
+    first = [0]
+    for fq in fqs:
+        first.append(first[-1] + fq.n)
+    n = first[-1]
+    B = max(1, min(int(args.batch), n))
+    dev = torch.device("cuda", args.device)
+    pipe = S.Pipeline(ix, cs, starts, L, B, dedup_capacity=max(n, 1), var_len=bool(M))
+    pipe.reset()
+    pipe.set_samples(first)
+    counts = torch.zeros((len(fqs), len(starts)), dtype=torch.int64, device=dev)
+    host = torch.empty((2 * B, L), dtype=torch.uint8).pin_memory()
+    d_reads = torch.empty((2 * B, L), dtype=torch.uint8, device=dev)
+    s = 0
+    for b0 in range(0, n, B):
+        b = min(B, n - b0)
+        q = b0
+        while q < b0 + b:   # the samples that overlap the batch, in order
+            while first[s + 1] <= q:
+                s += 1
+            e = min(b0 + b, first[s + 1])
+            fqs[s].pack(q - first[s], e - first[s], host[2 * (q - b0):2 * (e - b0)])
+            q = e
+        d_reads[:2 * b].copy_(host[:2 * b])
+        pipe.count_batches(d_reads, b, B, counts)
+        torch.cuda.synchronize(dev)   # (the host rows are packed again next trip)
+    st = pipe.stats(raise_on_error=False)
+    if st.error:
+        raise SystemExit("%s: %s" % (_err_label(st.error), S.ERRORS.get(st.error, st.error)))
+    host_counts = counts.cpu().numpy()
+    empty = []
+    for (sid, _, _), c, ss in zip(samples, host_counts, pipe.sample_stats()):
+        if ss.kept == 0:   # (count ID stops there with nothing written, varbin.py:96)
+            empty.append(sid)
+            continue
+        write_varbin(rows, c, ss.positions, ss.dups, ss.kept, sid + ".varbin.txt",
+                     sid + ".stats.txt")
+    if empty:
+        raise SystemExit("ZeroDivisionError: no read kept (varbin.py:96): " + " ".join(empty))
+
+
 def cmd_varbin(args):
     import torch
     chrominfo = S.read_chrom_sizes(args.chrom_sizes)
@@ -755,6 +842,19 @@ def main(argv=None):
                            help="distinct pair keys the de-dup set holds (0: sized from "
                                 "the input files)")
         p.set_defaults(fn=fn)
+    p = sub.add_parser("count-many", help="count every sample of MANIFEST (ID<TAB>r1 files<TAB>"
+                       "r2 files per line) in one run")
+    p.add_argument("manifest")
+    p.add_argument("bindir")
+    p.add_argument("--chrom-sizes", default=None)
+    p.add_argument("--batch", type=int, default=2_000_000, help="pairs per device batch")
+    p.add_argument("--verify", action="store_true",
+                   help="prove the index cache on the device before it is used")
+    p.add_argument("--max-read-len", type=int, default=0, metavar="N",
+                   help="mates of mixed lengths up to N bases")
+    p.add_argument("--presorted", action="store_true",
+                   help="every sample's files are in samtools sort -n order already")
+    p.set_defaults(fn=cmd_count_many)
     p = sub.add_parser("bins", help="design OUTDIR/bins.txt and gc.txt: NBINS bins holding equal "
                                     "numbers of uniquely mappable K-mer starts")
     p.add_argument("nbins", type=int)

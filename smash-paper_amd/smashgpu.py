@@ -49,6 +49,7 @@ EXPORTS = [
     "smash_phase_import", "smash_phase_positions", "smash_phase_bin",
     "smash_pipeline_stats", "smash_pipeline_reset", "smash_pipeline_reset_ex", "smash_pipeline_reads_resident", "smash_pipeline_peek",
     "smash_pipeline_var_len", "smash_pipeline_peek_lens", "smash_pipeline_peek_matches",
+    "smash_pipeline_samples", "smash_pipeline_sample_stats",
     "smash_pipeline_profile", "smash_pipeline_profile_read",
     "smash_pipeline_positions", "smash_bin_positions", "smash_mappability_scan",
     "smash_sam_records", "smash_sam_format", "smash_sam_free",
@@ -123,6 +124,16 @@ class Stats(C.Structure):
                 ("dupe_pairs", C.c_uint64), ("positions", C.c_uint64),
                 ("dups", C.c_uint64), ("kept", C.c_uint64),
                 ("matches", C.c_uint64), ("error", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class SampleStats(C.Structure):
+    """smash_sample_stats: one sample's counters of a run with a sample table"""
+    _fields_ = [("pairs", C.c_uint64), ("key_pairs", C.c_uint64),
+                ("dupe_pairs", C.c_uint64), ("positions", C.c_uint64),
+                ("dups", C.c_uint64), ("kept", C.c_uint64)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -207,6 +218,8 @@ def lib():
     L.smash_phase_positions.argtypes = [vp, vp, vp]
     L.smash_phase_bin.argtypes = [vp, vp, vp, vp]
     L.smash_pipeline_stats.argtypes = [vp, C.POINTER(Stats)]
+    L.smash_pipeline_samples.argtypes = [vp, u64p, C.c_uint32]
+    L.smash_pipeline_sample_stats.argtypes = [vp, C.POINTER(SampleStats), C.c_uint32]
     L.smash_pipeline_reset.argtypes = [vp, vp]
     L.smash_pipeline_reset_ex.argtypes = [vp, C.c_uint32, vp]
     L.smash_pipeline_reads_resident.argtypes = [vp, C.c_int]
@@ -626,6 +639,7 @@ class Pipeline:
         self.max_pairs = max_pairs
         self.slots = read_len - min_len + 1
         self.var_len = False
+        self.n_samples = 0
         if var_len:
             self.set_var_len(True)
 
@@ -637,10 +651,44 @@ class Pipeline:
         check(lib().smash_pipeline_var_len(self.h, 1 if on else 0), "smash_pipeline_var_len")
         self.var_len = bool(on)
 
+    def set_samples(self, first):
+        """the sample table of the runs to come (smash_pipeline_samples):
+        sample s is the run's pairs [first[s], first[s + 1]), first[0] = 0,
+        ascending; None or an empty table: the plain run again.  Right after a
+        reset (or before the first batch) only.  count_batch / count_batches
+        then take a [len(first) - 1, nbins] counts tensor, one row per sample."""
+        f = np.ascontiguousarray([] if first is None else first, np.uint64)
+        if f.ndim != 1 or len(f) == 1:
+            raise SmashError("set_samples: first holds the samples' starts and the run's end")
+        n = max(len(f) - 1, 0)
+        check(lib().smash_pipeline_samples(self.h, _p(f, u64p) if n else None, n),
+              "smash_pipeline_samples")
+        self.n_samples = n
+
+    def sample_stats(self):
+        """the per-sample counters so far, a list of SampleStats
+        (smash_pipeline_sample_stats); synchronises"""
+        out = (SampleStats * max(self.n_samples, 1))()
+        check(lib().smash_pipeline_sample_stats(self.h, out, self.n_samples),
+              "smash_pipeline_sample_stats")
+        return list(out[:self.n_samples])
+
+    def _counts(self, d_counts):
+        """the counts' pointer; with a sample table set a tensor must hold a
+        row of bins per sample (the kernels add into every sample's row)"""
+        rows = self.n_samples
+        if rows and d_counts is not None and not isinstance(d_counts, int):
+            if d_counts.numel() < rows * len(self.bins) or d_counts.element_size() != 8 or \
+                    not d_counts.is_contiguous():
+                raise SmashError("counts tensor: %d x %d contiguous 64-bit counters needed"
+                                 % (rows, len(self.bins)))
+        return _ptr(d_counts)
+
     def count_batch(self, d_reads, n_pairs, d_counts, stream=None):
-        """d_reads: device uint8 [2*n_pairs, read_len] (torch tensor or ptr)."""
+        """d_reads: device uint8 [2*n_pairs, read_len] (torch tensor or ptr);
+        d_counts: int64 [nbins], or [samples, nbins] with a sample table set."""
         check(lib().smash_count_batch(self.h, _reads(d_reads, n_pairs, self.stride), n_pairs,
-                                      _ptr(d_counts),
+                                      self._counts(d_counts),
                                       vp(_stream(stream))), "smash_count_batch")
 
     def count_fastq(self, r1_paths, r2_paths, d_counts, sort_names=True, threads=0,
@@ -668,12 +716,13 @@ class Pipeline:
         if resident:
             check(lib().smash_count_batches_ready(self.h, _reads(d_reads, n_pairs, self.stride),
                                                   n_pairs, batch_pairs,
-                                                  _ptr(d_counts), vp(_stream(stream)), None),
+                                                  self._counts(d_counts), vp(_stream(stream)),
+                                                  None),
                   "smash_count_batches_ready")
             return
         check(lib().smash_count_batches(self.h, _reads(d_reads, n_pairs, self.stride), n_pairs,
                                         batch_pairs,
-                                        _ptr(d_counts), vp(_stream(stream))),
+                                        self._counts(d_counts), vp(_stream(stream))),
               "smash_count_batches")
 
     def phase_map(self, d_reads, n_pairs, stream=None):
@@ -1249,6 +1298,7 @@ class FastqIndex:
             pass
 
 
+SMASH_ERR_ARG = -1
 SMASH_ERR_NOMEM = -4
 SMASH_ERR_UNSUPPORTED = -5
 
