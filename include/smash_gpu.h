@@ -519,7 +519,9 @@ int smash_pipeline_stats(smash_pipeline *p, smash_stats *out);
  * run under way.  Synchronous (it waits for the device).  With a table set a
  * batch that would take the run past h_first[n_samples] is SMASH_ERR_ARG when
  * it is queued, and the multi-GPU phase calls and smash_count_fastq return
- * SMASH_ERR_UNSUPPORTED.  Variable-length mode works as without a table. */
+ * SMASH_ERR_UNSUPPORTED (a multi-GPU run takes its table from
+ * smash_pipeline_samples_sharded, below).  Variable-length mode works as
+ * without a table. */
 int smash_pipeline_samples(smash_pipeline *p, const uint64_t *h_first, uint32_t n_samples);
 typedef struct {
   uint64_t pairs, key_pairs, dupe_pairs, positions, dups, kept;   /* as smash_stats */
@@ -529,6 +531,46 @@ typedef struct {
  * (matches and error stay run-wide: smash_pipeline_stats, whose other
  * counters are the sums over the samples).  Synchronises. */
 int smash_pipeline_sample_stats(smash_pipeline *p, smash_sample_stats *out, uint32_t cap);
+
+/* ---- many samples across GPUs --------------------------------------------- */
+/* The sample table of a multi-GPU run: sample s is the pairs [h_first[s],
+ * h_first[s + 1]) of the WHOLE run in its global order (step, rank, pair) --
+ * the index space of smash_phase_export's global_base -- not of this rank's
+ * own pairs, which is why this is a second entry point.  Every rank sets the
+ * same table.  Validation and lifetime as smash_pipeline_samples (ascending,
+ * h_first[0] = 0, at most 65535 samples, SMASH_ERR_ARG once a phase call of
+ * the run has taken pairs, kept across resets, n_samples = 0 clears it); a
+ * pipeline holds one kind of table at a time: setting either replaces the
+ * other.  With a sharded table set
+ *  - the phase calls work and every sample comes out as a run of its own
+ *    pairs alone, summed over the ranks; smash_count_batch* and
+ *    smash_count_fastq return SMASH_ERR_UNSUPPORTED;
+ *  - smash_phase_export takes pair i's sample from global_base + i
+ *    (SMASH_ERR_ARG when a non-empty batch passes h_first[n_samples]), chooses
+ *    the owner from the hash salted with the sample -- the same on every rank
+ *    -- and writes smash_phase_hdr_words() = 2 words per key into *d_send:
+ *    {nk << 40 | word offset, sample}.  (The first word has no 16 contiguous
+ *    free bits: 24 of word count, 40 of offset.)  The caller exchanges two
+ *    words per key; the plain layout and SMASH_EXPORT_HDR_WORDS stay as they
+ *    are without a table;
+ *  - smash_dedup_owner decides first-wins in receive order over the exact
+ *    (sample, key words): equal keys of two samples are both kept;
+ *  - smash_phase_positions writes d_tail[3] = {count, last pos0 or -1, the
+ *    sample of that position or -1}; smash_phase_bin reads d_prev[2] = {pos0,
+ *    sample} of the last position emitted before this rank's batch in the
+ *    global order (-1, -1: none), which opens the adjacent chain only of its
+ *    own sample, and adds into d_counts[n_samples][nbins].  Both take the
+ *    batch's global_base from the smash_phase_export before them;
+ *  - smash_pipeline_sample_stats returns this rank's share of every sample
+ *    (pairs: the pairs it exported); the sums over the ranks are the samples'
+ *    own runs.  The key and duplicate counts of a batch reach the rows with
+ *    its smash_phase_bin.
+ * The look-ahead searches and variable-length mode work as without a table. */
+int smash_pipeline_samples_sharded(smash_pipeline *p, const uint64_t *h_first,
+                                   uint32_t n_samples);
+/* u64 words per key in smash_phase_export's d_send and smash_dedup_owner's
+ * d_recv: SMASH_EXPORT_HDR_WORDS, or 2 with a sharded sample table set. */
+uint32_t smash_phase_hdr_words(const smash_pipeline *p);
 
 /* Kernel timing for the roofline: when enabled, HIP events are recorded on
  * the launch stream around the search kernel (k_mam) of every phase_map /

@@ -42,7 +42,10 @@ namespace {
 // samples start two probe chains, and compare the sample exactly wherever
 // they compare the words: a row record's is that of its pair g (a bisect
 // over the table, SampleTab::of), an arena record keeps sample + 1 in the high
-// half of its nk word (0 there: a record of a run without a table).
+// half of its nk word (0 there: a record of a run without a table).  An owner
+// of a run with a sharded table (smash_pipeline_samples_sharded) does the same
+// over its received keys (RecvSampleKeys): the sample comes in the header's
+// second word, every record is an arena record.
 constexpr int kRefShift = 40;
 // a published arena ref carries kRefPub; row refs and claims do not
 constexpr uint64_t kRefPub = 1ull << 39;
@@ -266,6 +269,12 @@ struct PairKeys {
   __device__ __forceinline__ uint32_t sample(uint64_t) const { return 0; }
 };
 
+// the hash hi of a key of sample smp: the exporter and the owner of a sharded
+// run must see one value; SamplePairKeys::key below holds the same expression
+__device__ __forceinline__ uint64_t sample_salt(uint64_t hi, uint32_t smp, uint64_t hmask) {
+  return (mix64(hi + (uint64_t(smp) + 1) * 0x9E3779B97F4A7C15ull) & hmask) | 1;
+}
+
 // the batch's pairs of a run with a sample table: PairKeys whose key includes
 // the pair's sample.  The hash hi is salted with it (hmask: the post stage's
 // hash mask, kept by the salted value too); lo stays the words' own, the
@@ -276,6 +285,9 @@ struct SamplePairKeys : PairKeys {
   uint64_t hmask;
   __device__ __forceinline__ uint32_t sample(uint64_t q) const { return tab.of(row_base + q); }
   __device__ __forceinline__ KeyRef key(uint64_t q, uint64_t *hi = nullptr) const {
+    // (sample_salt's expression, spelled out: with the call in its place
+    // k_dedup_claim_smp, a kernel of the single-GPU sample run, came out with
+    // other registers and one instruction fewer, and it is to keep its code)
     if (hi)
       *hi = (mix64(hash[2 * q] + (uint64_t(sample(q)) + 1) * 0x9E3779B97F4A7C15ull) & hmask) | 1;
     const int32_t k = nk[q];
@@ -315,6 +327,32 @@ struct RecvKeys {
     return k;
   }
   __device__ __forceinline__ uint32_t sample(uint64_t) const { return 0; }
+};
+
+// an owner's received keys of a run with a sharded sample table
+// (smash_pipeline_samples_sharded): the header has a second word, the sample
+// of the key's pair, which the exporter took from the pair's global index
+// (kHdrWordsSmp words per key).  The hash hi is salted with it exactly as
+// SamplePairKeys salts it -- the exporter chose this owner from the same
+// value -- and the sample is compared beside the words
+struct RecvSampleKeys : RecvKeys {
+  static constexpr bool kSamples = true;
+  __device__ __forceinline__ int32_t count(uint64_t j) const {
+    return int32_t(recv[kHdrWordsSmp * j] >> 40);
+  }
+  __device__ __forceinline__ uint32_t sample(uint64_t j) const {
+    return uint32_t(recv[kHdrWordsSmp * j + 1]);
+  }
+  __device__ __forceinline__ KeyRef key(uint64_t j, uint64_t *hi = nullptr) const {
+    int r = 0;
+    while (r + 1 < world && j >= base[r + 1]) ++r;
+    const uint64_t nw = recv[kHdrWordsSmp * j];
+    KeyRef k{words + base[65 + r] + (nw & kHdrOffMask), uint32_t(nw >> 40), 0};
+    uint64_t h = 0;
+    key_hashes(k.w, k.nk, hmask, h, k.lo);
+    if (hi) *hi = sample_salt(h, sample(j), hmask);
+    return k;
+  }
 };
 
 // The claim of key j (see above): its slot_of value.  err: the first error
@@ -370,16 +408,18 @@ __device__ __forceinline__ uint64_t claim_key(const Src &src, uint64_t j, const 
           }
         } else if (src.claimed(ref, epoch, j2)) {
           if (src.sample(j2) == smp && same_key(me, src.key(j2))) {
-            src.contest[j2] = 1;
+            if constexpr (Src::kMarks) src.contest[j2] = 1;
             atomicMin(sr, mine);
             res = i;
             break;
           }
         } else if ((ref >> kRefShift) == 0) {
-          if (src.tab.of(ref - 1) == smp && same_key(st, ref - 1, me)) {
-            res = kSlotOld;
-            break;
-          }
+          // (row refs are a pair source's: an owner's set holds arena refs only)
+          if constexpr (Src::kMarks)
+            if (src.tab.of(ref - 1) == smp && same_key(st, ref - 1, me)) {
+              res = kSlotOld;
+              break;
+            }
         }
       } else if (ref & kRefPub) {
         if ((ref >> kRefShift) != epoch &&
@@ -602,6 +642,33 @@ __global__ void k_owner_decide(const uint64_t *recv, const uint64_t *words, cons
                                const uint64_t *__restrict__ slot_of, uint8_t *flags,
                                unsigned long long *stats, uint64_t hmask) {
   const RecvKeys src{recv, words, base, world, hmask};
+  const bool full = decide_keys(src, n, table, arena, arena_cap, arena_top, epoch, slot_of,
+                                [&](uint64_t j, bool win) __attribute__((always_inline)) {
+                                  flags[j] = win ? 1 : 0;
+                                });
+  if (full) atomicCAS(&stats[S_ERR], 0ull, (unsigned long long)(unsigned)SMASH_ERR_NOMEM);
+}
+
+// the owner's two kernels over RecvSampleKeys (a sharded sample table is set)
+__global__ void k_owner_claim_smp(const uint64_t *recv, const uint64_t *words,
+                                  const uint64_t *base, int world, uint64_t n, KeyStore st,
+                                  uint64_t epoch, uint64_t *slot_of, unsigned long long *stats,
+                                  uint64_t hmask) {
+  const RecvSampleKeys src{{recv, words, base, world, hmask}};
+  const uint64_t stride = uint64_t(gridDim.x) * blockDim.x;
+  int32_t err = 0;
+  for (uint64_t j = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; j < n; j += stride)
+    slot_of[j] = claim_key(src, j, st, epoch, err);
+  if (err) atomicCAS(&stats[S_ERR], 0ull, (unsigned long long)(unsigned)err);
+}
+
+__global__ void k_owner_decide_smp(const uint64_t *recv, const uint64_t *words,
+                                   const uint64_t *base, int world, uint64_t n, uint64_t *table,
+                                   uint64_t *arena, uint64_t arena_cap,
+                                   unsigned long long *arena_top, uint64_t epoch,
+                                   const uint64_t *__restrict__ slot_of, uint8_t *flags,
+                                   unsigned long long *stats, uint64_t hmask) {
+  const RecvSampleKeys src{{recv, words, base, world, hmask}};
   const bool full = decide_keys(src, n, table, arena, arena_cap, arena_top, epoch, slot_of,
                                 [&](uint64_t j, bool win) __attribute__((always_inline)) {
                                   flags[j] = win ? 1 : 0;

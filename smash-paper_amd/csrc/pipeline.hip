@@ -45,6 +45,11 @@ constexpr uint32_t kStatStride = 16, kStatStripes = 16, kStatWords = kStatStride
 constexpr uint32_t kHdrWords = 1;
 constexpr uint64_t kHdrOffMask = (uint64_t(1) << 40) - 1;
 static_assert(kHdrWords == SMASH_EXPORT_HDR_WORDS, "smash_gpu.h's export header");
+// with a sharded sample table (smash_pipeline_samples_sharded) a second header
+// word carries the sample of the key's pair: the first word has 24 bits of
+// word count and 40 of offset, neither with 16 bits to spare at the largest
+// batch (smash_phase_hdr_words)
+constexpr uint32_t kHdrWordsSmp = 2;
 }  // namespace
 
 // The post-stage kernels run beside the next batch's k_mam_sm (no LDS, so
@@ -173,7 +178,17 @@ struct smash_pipeline {
   std::vector<uint64_t> h_first;
   uint64_t *d_first = nullptr;
   unsigned long long *d_sstats = nullptr;
-  uint32_t bin_short = 0;         // the sample-aware emit kernel's short-run threshold (pairs)
+  // smash_pipeline_samples_sharded: the table is over the global pair indexes
+  // of a multi-GPU run.  g_base: the current batch's global_base (set by
+  // smash_phase_export, read by the positions and bin phases); phase_pairs:
+  // the pairs the phase calls took since the last reset; h_spairs[s]: this
+  // rank's pairs of sample s so far; hdr_cap: the words per key d_send_hdr
+  // is allocated for
+  bool sharded = false;
+  uint64_t g_base = 0, phase_pairs = 0;
+  std::vector<uint64_t> h_spairs;
+  uint32_t hdr_cap = 1;
+  uint32_t bin_short = 0;        // the sample-aware emit kernel's short-run threshold (pairs)
   uint32_t *d_fb = nullptr;       // [1 + max_pairs]: k_post_fast<16> -> k_post pair list
   uint32_t *d_l16 = nullptr;      // [1 + max_pairs]: k_post_fast<8> -> k_post_fast<16>
   uint8_t *d_post_ws = nullptr;   // k_post workspace: kPostThreads slices
@@ -1555,6 +1570,44 @@ __global__ void k_tail_lps_smp(const uint32_t *posoff, const int64_t *lps, uint6
   else if (fs >= row_base) prev[0] = -1;
 }
 
+// A rank's batch of a multi-GPU run with a sharded sample table
+// (smash_pipeline_samples_sharded) runs k_emit_bin_smp as it is: the hit rows
+// are the batch's own, and the kernel's row_base, which it uses for the table
+// lookups only, is the batch's global base.  What differs is the line carried
+// into the batch and the one it hands on, both of which name their sample:
+// the ranks between two emitting shards may hold a sample boundary.
+//
+// k_prev_shard: prev_in = {pos0, sample} of the last position emitted before
+// this batch in the global order ({-1, -1}: none).  The kernel above opens a
+// chain with *prev_p only for the sample that began before the batch, the one
+// that holds the batch's first pair (g_base < first[n]): the line is that
+// sample's or it is none.
+__global__ void k_prev_shard(const int64_t *prev_in, uint64_t g_base, SampleTab tab,
+                             int64_t *prev) {
+  prev[0] = prev_in[0] >= 0 && prev_in[1] == int64_t(tab.of(g_base)) ? prev_in[0] : -1;
+}
+
+// k_tail_shard: tail = {positions emitted, the last one's pos0, its sample}
+// ({0, -1, -1}: none).  The last emitting pair is the one before the first q
+// with posoff[q] = posoff[n] (posoff[q]: the positions emitted before pair q).
+__global__ void k_tail_shard(const uint32_t *posoff, const int64_t *lps, uint64_t n,
+                             uint64_t g_base, SampleTab tab, int64_t *tail) {
+  const uint32_t c = n ? posoff[n] : 0u;
+  int64_t last = -1, smp = -1;
+  if (c) {
+    uint64_t lo = 0, hi = n;   // (posoff[0] = 0 < c: lo ends at 1 or above)
+    while (lo < hi) {
+      const uint64_t mid = (lo + hi) >> 1;
+      if (posoff[mid] < c) lo = mid + 1; else hi = mid;
+    }
+    last = lps[n - 1];
+    smp = int64_t(tab.of(g_base + lo - 1));
+  }
+  tail[0] = int64_t(c);
+  tail[1] = last;
+  tail[2] = smp;
+}
+
 // the batch's tail {count, last position} (lps_last: lps[n - 1]; count 0:
 // -1) and the carried line for the next batch
 __global__ void k_tail_lps(const uint32_t *npos_p, const int64_t *lps_last, int64_t *prev,
@@ -2062,10 +2115,18 @@ static int phase_map_impl(smash_pipeline *p, const uint8_t *d_reads, uint64_t n_
   return SMASH_OK;
 }
 
-// the multi-GPU phase calls and the file feed take no sample table
+// the multi-GPU phase calls take a sample table over the global pair indexes
+// only (smash_pipeline_samples_sharded): smash_pipeline_samples' counts the
+// rank's own pairs
 static int no_samples(const smash_pipeline *p, const char *what) {
-  if (!p || p->h_first.empty()) return SMASH_OK;
+  if (!p || p->h_first.empty() || p->sharded) return SMASH_OK;
   set_error(std::string(what) + ": not supported while a sample table is set");
+  return SMASH_ERR_UNSUPPORTED;
+}
+// the single-GPU batch calls take no sharded table: they know no global index
+static int no_sharded(const smash_pipeline *p, const char *what) {
+  if (!p || !p->sharded) return SMASH_OK;
+  set_error(std::string(what) + ": not supported while a sharded sample table is set");
   return SMASH_ERR_UNSUPPORTED;
 }
 namespace smash {
@@ -2075,15 +2136,19 @@ bool pipe_samples(const smash_pipeline *p) { return !p->h_first.empty(); }
 extern "C" int smash_phase_map(smash_pipeline *p, const uint8_t *d_reads,
                                uint64_t n_pairs, void *stream) {
   if (int rc = no_samples(p, "smash_phase_map")) return rc;
-  return phase_map_impl(p, d_reads, n_pairs, static_cast<hipStream_t>(stream), nullptr);
+  const int rc = phase_map_impl(p, d_reads, n_pairs, static_cast<hipStream_t>(stream), nullptr);
+  if (!rc) p->phase_pairs += n_pairs;
+  return rc;
 }
 
 extern "C" int smash_phase_map_ahead(smash_pipeline *p, const uint8_t *d_reads,
                                      uint64_t n_pairs, const uint8_t *d_next, uint64_t n_next,
                                      void *stream) {
   if (int rc = no_samples(p, "smash_phase_map_ahead")) return rc;
-  return phase_map_impl(p, d_reads, n_pairs, static_cast<hipStream_t>(stream), nullptr, d_next,
-                        n_next);
+  const int rc = phase_map_impl(p, d_reads, n_pairs, static_cast<hipStream_t>(stream), nullptr,
+                                d_next, n_next);
+  if (!rc) p->phase_pairs += n_pairs;
+  return rc;
 }
 
 // the search of the batch after the next one, into the set the current
@@ -2180,7 +2245,10 @@ static int positions_impl(smash_pipeline *p, int64_t *d_tail, hipStream_t s) {
     SMASH_HIP(hipGetLastError());
     p->pos_dirty = true;
   }
-  k_tail_lps<<<1, 1, 0, s>>>(p->d_posoff + n, p->d_lps + (n ? n - 1 : 0), nullptr, d_tail);
+  if (p->sharded)   // (d_tail[3]: the last position's sample travels with it)
+    k_tail_shard<<<1, 1, 0, s>>>(p->d_posoff, p->d_lps, n, p->g_base, sample_tab(p), d_tail);
+  else
+    k_tail_lps<<<1, 1, 0, s>>>(p->d_posoff + n, p->d_lps + (n ? n - 1 : 0), nullptr, d_tail);
   SMASH_HIP(hipGetLastError());
   return SMASH_OK;
 }
@@ -2188,30 +2256,41 @@ static int positions_impl(smash_pipeline *p, int64_t *d_tail, hipStream_t s) {
 extern "C" int smash_phase_positions(smash_pipeline *p, int64_t *d_tail, void *stream) {
   if (!p) return SMASH_ERR_ARG;
   if (int rc = no_samples(p, "smash_phase_positions")) return rc;
+  if (p->sharded && !d_tail) return SMASH_ERR_ARG;
   return positions_impl(p, d_tail, static_cast<hipStream_t>(stream));
 }
 
 // the batch's emit + bin with a sample table set: d_counts is [S][nbins], the
 // chain, the rows and the counters per sample (k_emit_bin_smp)
-static int bin_samples(smash_pipeline *p, uint64_t *d_counts, hipStream_t s) {
+//
+// shard_prev (a sharded table, smash_phase_bin): the table is looked up at the
+// batch's global base instead of the run's rows before it (the hit rows stay
+// the batch's own), the carried line is the caller's {pos0, sample} after
+// k_prev_shard's sample check, and nothing is carried on: the next batch's
+// line comes from the caller again
+static int bin_samples(smash_pipeline *p, uint64_t *d_counts, hipStream_t s,
+                       const int64_t *shard_prev = nullptr) {
   const uint64_t n = p->n_pairs;
   if (!n) return SMASH_OK;
   const SampleTab tab = sample_tab(p);
+  const uint64_t look = shard_prev ? p->g_base : p->row_base;
+  if (shard_prev) k_prev_shard<<<1, 1, 0, s>>>(shard_prev, look, tab, p->d_prev);
   unsigned long long *counts = reinterpret_cast<unsigned long long *>(d_counts);
   if (p->bin_lds) {   // (set only when parts <= kBinPartsMax)
     const unsigned gx = unsigned(std::min<uint64_t>(kBinBlocks, (n + 1023) / 1024));
     k_emit_bin_smp<true><<<dim3(gx, bin_parts(p->nbins)), 1024, 0, s>>>(
         p->d_keep, pair_nk(p), hit_rows(p), p->d_chrom_off, p->d_lps, p->d_posoff, n,
-        p->row_base, tab, p->d_prev, p->d_bins, p->nbins, p->d_cell, p->ncell, p->cshift, counts,
+        look, tab, p->d_prev, p->d_bins, p->nbins, p->d_cell, p->ncell, p->cshift, counts,
         p->d_stats, p->d_sstats, bin_part_size(p->nbins), p->bin_flush, p->bin_short);
   } else {
     k_emit_bin_smp<false><<<grid_for(n, kB, 8192), kB, 0, s>>>(
         p->d_keep, pair_nk(p), hit_rows(p), p->d_chrom_off, p->d_lps, p->d_posoff, n,
-        p->row_base, tab, p->d_prev, p->d_bins, p->nbins, p->d_cell, p->ncell, p->cshift, counts,
+        look, tab, p->d_prev, p->d_bins, p->nbins, p->d_cell, p->ncell, p->cshift, counts,
         p->d_stats, p->d_sstats, 0, 0, 0);
   }
   SMASH_HIP(hipGetLastError());
-  k_tail_lps_smp<<<1, 1, 0, s>>>(p->d_posoff, p->d_lps, n, p->row_base, tab, p->d_prev);
+  if (!shard_prev)
+    k_tail_lps_smp<<<1, 1, 0, s>>>(p->d_posoff, p->d_lps, n, p->row_base, tab, p->d_prev);
   SMASH_HIP(hipGetLastError());
   return SMASH_OK;
 }
@@ -2248,6 +2327,11 @@ extern "C" int smash_phase_bin(smash_pipeline *p, const int64_t *d_prev,
                                uint64_t *d_counts, void *stream) {
   if (!p || !d_counts) return SMASH_ERR_ARG;
   if (int rc = no_samples(p, "smash_phase_bin")) return rc;
+  if (p->sharded) {
+    if (!d_prev) return SMASH_ERR_ARG;
+    p->last = static_cast<hipStream_t>(stream);
+    return bin_samples(p, d_counts, p->last, d_prev);
+  }
   return bin_impl(p, d_prev, d_counts, static_cast<hipStream_t>(stream));
 }
 
@@ -2257,6 +2341,7 @@ int count_batch_ev(smash_pipeline *p, const uint8_t *d_reads, uint64_t n_pairs,
                    uint64_t *d_counts, hipStream_t s, hipEvent_t in_ev) {
   // (the host knows the run's pairs at this point: nothing is queued for a
   // batch that would pass the table's end)
+  if (int rc = no_sharded(p, "smash_count_batch")) return rc;
   if (p && !p->h_first.empty() && p->row_next + n_pairs > p->h_first.back()) {
     set_error("smash_count_batch: the batch takes the run past the sample table's last pair");
     return SMASH_ERR_ARG;
@@ -2488,6 +2573,112 @@ __global__ __launch_bounds__(kB) void k_export_fill(const int32_t *nk, const uin
   }
 }
 
+// The export's sample forms (a sharded sample table is set,
+// smash_pipeline_samples_sharded): pair q of the batch is pair g_base + q of
+// the whole run, its sample is the table's, its owner is taken from the hash
+// hi salted with the sample (sample_salt: the value the owner's set sees, so
+// every rank sends the keys of one sample's pair list to one owner), and the
+// header has a second word, the sample (kHdrWordsSmp).  The grouping and the
+// offsets are k_export_count's / k_export_fill's (see there).  The plain
+// kernels keep their own text: with their bodies moved into functions shared
+// with these forms (a template over the owner rule, inlined) the compiler
+// placed the load of the block size and the first branches differently in
+// both (k_export_count 513 -> 520 lines of gfx950 assembly, k_export_fill
+// 819 -> 826), and the plain kernels are to keep their machine code.  The
+// parts that do not depend on the owner rule are functions here.
+struct SampleOwner {
+  uint64_t g_base;
+  SampleTab tab;
+  uint64_t hmask;
+  __device__ __forceinline__ uint32_t owner(const uint64_t *hash, uint64_t q, int world,
+                                            uint32_t &smp) const {
+    smp = tab.of(g_base + q);
+    return uint32_t(key_owner(sample_salt(hash[2 * q], smp, hmask), world));
+  }
+};
+// the per-wave group tables cleared (the block's barrier included)
+__device__ __forceinline__ void export_clear(uint32_t (*s_e)[64], uint32_t (*s_w)[64]) {
+  for (uint32_t o = threadIdx.x; o < kExWaves * 64; o += blockDim.x) {
+    (&s_e[0][0])[o] = 0;
+    (&s_w[0][0])[o] = 0;
+  }
+  __syncthreads();
+}
+// the block's keys and words of owner o over the waves before wave `upto`
+__device__ __forceinline__ void export_sum(const uint32_t (*s_e)[64], const uint32_t (*s_w)[64],
+                                           uint32_t o, uint32_t upto, uint64_t &e, uint64_t &w) {
+  for (uint32_t v = 0; v < upto; ++v) {
+    e += s_e[v][o];
+    w += s_w[v][o];
+  }
+}
+// the wave's keys copied by the whole wave (k_export_fill's last loop): lane
+// l's k words from its hit row to words[w ...]; every lane calls it
+__device__ __forceinline__ void wave_copy_keys(uint32_t k, uint64_t w, const uint64_t *row,
+                                               uint64_t *words) {
+  const uint32_t lane = threadIdx.x & 63;
+  uint32_t total;
+  const uint32_t incl = wave_incl(k, total);
+  const uint64_t rowv = reinterpret_cast<uint64_t>(row);
+  for (uint32_t t0 = 0; t0 < total; t0 += 64) {   // (wave-uniform: every shuffle has all lanes)
+    const uint32_t t = t0 + lane;
+    uint32_t before;
+    const uint32_t l = wave_word_owner(incl, t, before);
+    const uint64_t wl = __shfl(w, int(l), 64), rl = __shfl(rowv, int(l), 64);
+    if (t < total) words[wl + (t - before)] = reinterpret_cast<const uint64_t *>(rl)[t - before];
+  }
+}
+
+__global__ __launch_bounds__(kB) void k_export_count_smp(const int32_t *nk, const uint64_t *hash,
+                                                         uint64_t n, int world, uint32_t nblk,
+                                                         uint64_t *bc, SampleOwner ex) {
+  __shared__ uint32_t s_e[kExWaves][64], s_w[kExWaves][64];
+  const uint32_t wv = threadIdx.x >> 6;
+  export_clear(s_e, s_w);
+  const uint64_t q = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  const bool act = q < n && nk[q] >= 0;
+  uint32_t smp = 0;
+  const uint32_t ow = act ? ex.owner(hash, q, world, smp) : 0u;
+  (void)wave_owner_groups(act, ow, act ? uint32_t(nk[q]) : 0u, s_e[wv], s_w[wv]);
+  __syncthreads();
+  for (uint32_t o = threadIdx.x; o < uint32_t(world); o += blockDim.x) {
+    uint64_t e = 0, w = 0;
+    export_sum(s_e, s_w, o, kExWaves, e, w);
+    bc[uint64_t(o) * nblk + blockIdx.x] = (e << 32) | w;
+  }
+}
+
+__global__ __launch_bounds__(kB) void k_export_fill_smp(const int32_t *nk, const uint64_t *hash,
+                                                        HitRows hits, uint64_t n, int world,
+                                                        uint32_t nblk, const uint64_t *boff,
+                                                        uint64_t *hdr, uint64_t *words,
+                                                        uint32_t *send_q, SampleOwner ex) {
+  __shared__ uint32_t s_e[kExWaves][64], s_w[kExWaves][64];
+  const uint32_t wv = threadIdx.x >> 6;
+  export_clear(s_e, s_w);
+  const uint64_t q = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  const bool act = q < n && nk[q] >= 0;
+  uint32_t smp = 0;
+  const uint32_t ow = act ? ex.owner(hash, q, world, smp) : 0u;
+  const uint32_t k = act ? uint32_t(nk[q]) : 0u;
+  const WaveGroup g = wave_owner_groups(act, ow, k, s_e[wv], s_w[wv]);
+  __syncthreads();
+  uint64_t w = 0;
+  if (act) {
+    uint64_t e = g.rank;
+    w = g.wbefore;
+    export_sum(s_e, s_w, ow, wv, e, w);
+    const uint64_t bo = boff[uint64_t(ow) * nblk + blockIdx.x];
+    const uint64_t seg_w = boff[uint64_t(ow) * nblk] & 0xFFFFFFFFull;   // owner's word segment
+    e += bo >> 32;
+    w += bo & 0xFFFFFFFFull;
+    hdr[kHdrWordsSmp * e] = uint64_t(k) << 40 | (w - seg_w);   // offset in the owner's words
+    hdr[kHdrWordsSmp * e + 1] = smp;
+    send_q[e] = uint32_t(q);
+  }
+  wave_copy_keys(k, w, act ? hits.row(q, int32_t(k)) : nullptr, words);
+}
+
 __global__ void k_import(const uint8_t *flags, const uint32_t *send_q, uint64_t n_export,
                          uint8_t *keep) {
   const uint64_t o = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
@@ -2517,6 +2708,14 @@ extern "C" int smash_phase_export(smash_pipeline *p, int world, uint64_t global_
   hipStream_t s = static_cast<hipStream_t>(stream);
   p->last = s;
   const uint64_t n = p->n_pairs;
+  // (an empty share of a short last step may stand past the table's end)
+  if (p->sharded && n && global_base + n > p->h_first.back()) {
+    set_error("smash_phase_export: the batch passes the sample table's last pair");
+    return SMASH_ERR_ARG;
+  }
+  const SampleOwner sex{global_base, p->sharded ? sample_tab(p) : SampleTab{nullptr, 0},
+                         p->hash_mask};
+  if (p->sharded) p->g_base = global_base;   // the later phases' table lookups
   const uint32_t nblk = uint32_t(std::max<uint64_t>(1, (n + kB - 1) / kB));
   SMASH_HIP(hipMemsetAsync(p->d_keep, 0, n ? n : 1, s));
   // per-owner totals to the host (the collectives' split sizes): the one
@@ -2524,7 +2723,11 @@ extern "C" int smash_phase_export(smash_pipeline *p, int world, uint64_t global_
   unsigned long long *cnt = p->h_owner;
   std::fill(cnt, cnt + 128, 0ull);
   if (n) {
-    k_export_count<<<nblk, kB, 0, s>>>(pair_nk(p), p->d_hash, n, world, nblk, p->d_bcnt);
+    if (p->sharded)
+      k_export_count_smp<<<nblk, kB, 0, s>>>(pair_nk(p), p->d_hash, n, world, nblk, p->d_bcnt,
+                                             sex);
+    else
+      k_export_count<<<nblk, kB, 0, s>>>(pair_nk(p), p->d_hash, n, world, nblk, p->d_bcnt);
     size_t tb = p->scan_temp_bytes;
     SMASH_HIP(hipcub::DeviceScan::ExclusiveSum(p->d_scan_temp, tb, p->d_bcnt, p->d_boff,
                                                uint64_t(world) * nblk, s));
@@ -2546,12 +2749,24 @@ extern "C" int smash_phase_export(smash_pipeline *p, int world, uint64_t global_
     p->send_words_cap = wtot + wtot / 4 + 1024;
     SMASH_HIP(hipMalloc(&p->d_send_words, 8 * p->send_words_cap));
   }
-  if (n)
+  if (n && p->sharded)
+    k_export_fill_smp<<<nblk, kB, 0, s>>>(pair_nk(p), p->d_hash, hit_rows(p), n, world, nblk,
+                                          p->d_boff, p->d_send_hdr, p->d_send_words, p->d_send_q,
+                                          sex);
+  else if (n)
     k_export_fill<<<nblk, kB, 0, s>>>(pair_nk(p), p->d_hash, hit_rows(p), n, world, nblk,
                                       p->d_boff, p->d_send_hdr, p->d_send_words, p->d_send_q);
   SMASH_HIP(hipGetLastError());
   *d_send = p->d_send_hdr;
   *d_send_words = p->d_send_words;
+  // this rank's pairs per sample, once the export is queued whole
+  for (uint64_t g = global_base; p->sharded && g < global_base + n;) {
+    const size_t k = size_t(std::upper_bound(p->h_first.begin(), p->h_first.end() - 1, g) -
+                            p->h_first.begin()) - 1;
+    const uint64_t e = std::min(global_base + n, p->h_first[k + 1]);
+    p->h_spairs[k] += e - g;
+    g = e;
+  }
   return SMASH_OK;
 }
 
@@ -2598,6 +2813,17 @@ extern "C" int smash_dedup_owner(smash_pipeline *p, const uint64_t *d_recv, uint
   SMASH_HIP(hipMemcpyAsync(p->d_recv_base, base, 8 * 2 * 65, hipMemcpyHostToDevice, s));
   SMASH_HIP(hipEventRecord(p->ev_base, s));
   const uint64_t epoch = next_epoch(p);
+  if (p->sharded) {   // d_recv: kHdrWordsSmp words per key, the second its sample
+    k_owner_claim_smp<<<grid_for(n_recv, kB, 8192), kB, 0, s>>>(
+        d_recv, d_recv_words, p->d_recv_base, world, n_recv, key_store(p), epoch, p->d_oslot,
+        p->d_stats, p->hash_mask);
+    SMASH_HIP(hipGetLastError());
+    k_owner_decide_smp<<<grid_for((n_recv + kDecGroups - 1) / kDecGroups, kB, 8192), kB, 0, s>>>(
+        d_recv, d_recv_words, p->d_recv_base, world, n_recv, p->d_table, p->d_arena,
+        p->arena_cap, p->d_arena_top, epoch, p->d_oslot, d_flags, p->d_stats, p->hash_mask);
+    SMASH_HIP(hipGetLastError());
+    return SMASH_OK;
+  }
   k_owner_claim<<<grid_for(n_recv, kB, 8192), kB, 0, s>>>(
       d_recv, d_recv_words, p->d_recv_base, world, n_recv, key_store(p), epoch, p->d_oslot,
       p->d_stats, p->hash_mask);
@@ -2662,10 +2888,11 @@ extern "C" int smash_pipeline_stats(smash_pipeline *p, smash_stats *o) {
 // The sample table of the runs to come (smash_gpu.h): legal while the run has
 // no batch yet.  Synchronous: it waits for the device, since the previous
 // run's queued kernels may still read the table it replaces.
-extern "C" int smash_pipeline_samples(smash_pipeline *p, const uint64_t *h_first,
-                                      uint32_t n_samples) {
+static int set_samples(smash_pipeline *p, const uint64_t *h_first, uint32_t n_samples,
+                       bool sharded) {
   if (!p || (n_samples && !h_first)) return SMASH_ERR_ARG;
-  if (p->row_next) {
+  // (a sharded run advances no rows: its pairs are the phase calls')
+  if (p->row_next || ((sharded || p->sharded) && p->phase_pairs)) {
     set_error("smash_pipeline_samples: a run is under way (set the table at a reset)");
     return SMASH_ERR_ARG;
   }
@@ -2686,6 +2913,17 @@ extern "C" int smash_pipeline_samples(smash_pipeline *p, const uint64_t *h_first
   SMASH_HIP(hipDeviceSynchronize());
   uint64_t *f = nullptr;
   unsigned long long *st = nullptr;
+  if (n_samples && sharded && p->hdr_cap < kHdrWordsSmp) {   // two header words per key
+    uint64_t *h = nullptr;
+    if (hipMalloc(reinterpret_cast<void **>(&h), 8 * uint64_t(kHdrWordsSmp) * p->max_pairs) !=
+        hipSuccess) {
+      set_error("smash_pipeline_samples_sharded: out of device memory");
+      return SMASH_ERR_NOMEM;
+    }
+    dfree(p->d_send_hdr);
+    p->d_send_hdr = h;
+    p->hdr_cap = kHdrWordsSmp;
+  }
   if (n_samples) {
     if (hipMalloc(reinterpret_cast<void **>(&f), 8 * (uint64_t(n_samples) + 1)) != hipSuccess ||
         hipMalloc(reinterpret_cast<void **>(&st), 8 * SS_N * uint64_t(n_samples)) != hipSuccess) {
@@ -2702,7 +2940,23 @@ extern "C" int smash_pipeline_samples(smash_pipeline *p, const uint64_t *h_first
   p->d_sstats = st;
   if (n_samples) p->h_first.assign(h_first, h_first + n_samples + 1);
   else p->h_first.clear();
+  p->sharded = sharded && n_samples;
+  p->h_spairs.assign(p->sharded ? n_samples : 0, 0);
   return SMASH_OK;
+}
+
+extern "C" int smash_pipeline_samples(smash_pipeline *p, const uint64_t *h_first,
+                                      uint32_t n_samples) {
+  return set_samples(p, h_first, n_samples, false);
+}
+
+extern "C" int smash_pipeline_samples_sharded(smash_pipeline *p, const uint64_t *h_first,
+                                              uint32_t n_samples) {
+  return set_samples(p, h_first, n_samples, true);
+}
+
+extern "C" uint32_t smash_phase_hdr_words(const smash_pipeline *p) {
+  return p && p->sharded ? kHdrWordsSmp : kHdrWords;
 }
 
 extern "C" int smash_pipeline_sample_stats(smash_pipeline *p, smash_sample_stats *out,
@@ -2719,7 +2973,9 @@ extern "C" int smash_pipeline_sample_stats(smash_pipeline *p, smash_sample_stats
   for (uint32_t k = 0; k < m; ++k) {
     const unsigned long long *r = st.data() + uint64_t(k) * SS_N;
     // the sample's pairs counted so far: the run's first row_next pairs
-    out[k].pairs = std::min(p->row_next, p->h_first[k + 1]) - std::min(p->row_next, p->h_first[k]);
+    out[k].pairs = p->sharded ? p->h_spairs[k]   // (this rank's exported pairs of the sample)
+                              : std::min(p->row_next, p->h_first[k + 1]) -
+                                    std::min(p->row_next, p->h_first[k]);
     out[k].key_pairs = r[SS_KEYPAIRS];
     out[k].dupe_pairs = r[SS_DUPEPAIRS];
     out[k].positions = r[SS_POS];
@@ -2861,6 +3117,8 @@ extern "C" int smash_pipeline_reset_ex(smash_pipeline *p, uint32_t flags, void *
   // rows (the search streams never touch them), so stream order keeps a new
   // row from landing under a reader of the old one.
   p->row_base = p->row_next = 0;
+  p->phase_pairs = 0;
+  std::fill(p->h_spairs.begin(), p->h_spairs.end(), uint64_t(0));
   SMASH_HIP(hipMemsetAsync(p->d_stats, 0, 8 * kStatWords, s));
   if (p->d_sstats)   // (the table itself stays: the new run has the same samples)
     SMASH_HIP(hipMemsetAsync(p->d_sstats, 0, 8 * SS_N * (p->h_first.size() - 1), s));

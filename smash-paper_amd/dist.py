@@ -17,6 +17,12 @@ the two dependencies the reference's sequential scripts carry:
   emitted position: all_gather of every rank's {count, last pos0} gives each
   rank the last position emitted before its shard.
 
+With a sample table (ShardedCounter(samples=first): a demultiplexed lane,
+sample s = global pairs [first[s], first[s + 1])) both dependencies are per
+sample: the headers carry each key's sample as a second word and the owner
+compares it beside the key, and the tails carry {count, last pos0, its
+sample}, so the line a rank inherits opens only its own sample's chain.
+
 Bin counts stay per rank until the caller's all_reduce.
 `pipe` is a smashgpu.Pipeline (device tensors, RCCL) or any object with the
 same phase_* methods (the CPU tests drive this code over gloo with an
@@ -91,7 +97,7 @@ class KeySetFull(RuntimeError):
 
 class ShardedCounter:
     def __init__(self, pipe, rank, world, device, group=None, count_group=None, comm=None,
-                 plan_pairs=0, key_slack=1 << 20):
+                 plan_pairs=0, key_slack=1 << 20, samples=None):
         """count_group: a CPU (gloo) process group for the per-batch key
         counts, which are host integers after smash_phase_export: exchanged
         there they cost no device synchronisation (None: over `group`).
@@ -104,13 +110,23 @@ class ShardedCounter:
         (its share of that batch's keys) x 1.125 + key_slack -- the owner
         skew measured, not assumed uniform.  Either way a set that overflows
         stops the run at the batch after the one that overflowed it
-        (KeySetFull), not after the pass."""
+        (KeySetFull), not after the pass.
+        samples: the run's sample table over its global pair indexes, the
+        same on every rank (pipe.set_samples_sharded): every sample is then
+        counted as a run of its own -- d_counts is [len(samples) - 1, nbins],
+        sample_stats() the per-sample statistics summed over the ranks."""
         self.pipe = pipe
         self.rank = rank
         self.world = world
         self.device = device
         self.comm = comm if comm is not None else TorchComm(device, group, count_group)
-        self.carried = torch.full((1,), -1, dtype=torch.int64, device=device)
+        self.samples = None if samples is None else [int(x) for x in samples]
+        if self.samples is not None:
+            pipe.set_samples_sharded(self.samples)
+        # a tail is {count, last pos0} and, with samples, that position's
+        # sample; the carried line is the tail without its count
+        self.tail_words = 3 if self.samples is not None else 2
+        self.carried = torch.full((self.tail_words - 1,), -1, dtype=torch.int64, device=device)
         self.max_pairs = pipe.max_pairs
         self.plan_pairs = int(plan_pairs)
         self.key_slack = int(key_slack)
@@ -240,10 +256,10 @@ class ShardedCounter:
         self.comm.all_to_all(back[:sum(snd)], flags[:n_recv], snd, rcv)
         self._mark("all_to_all_flags")
         p.phase_import(back)
-        tail = torch.empty(2, dtype=torch.int64, device=dev)
+        tail = torch.empty(self.tail_words, dtype=torch.int64, device=dev)
         p.phase_positions(tail)
         self._mark("import_positions")
-        parts = [torch.empty(2, dtype=torch.int64, device=dev) for _ in range(W)]
+        parts = [torch.empty(self.tail_words, dtype=torch.int64, device=dev) for _ in range(W)]
         self.comm.all_gather(parts, tail)
         tails = torch.stack(parts)
         prev = self._prev(tails[:r], self.carried)
@@ -255,14 +271,26 @@ class ShardedCounter:
     @staticmethod
     def _prev(tails, carried):
         """last pos0 of the latest non-empty shard among `tails` (rank order),
-        else the carried value -- on the device, no host sync."""
+        else the carried value -- on the device, no host sync.  Three-word
+        tails (a sample table): {pos0, sample} of that shard, else the carried
+        pair."""
         if tails.shape[0] == 0:
             return carried.clone()
         nonempty = tails[:, 0] > 0
         idx = torch.arange(tails.shape[0], device=tails.device)
         last = torch.where(nonempty, idx, torch.full_like(idx, -1)).max()
-        pick = tails[last.clamp(min=0), 1].reshape(1)
+        pick = tails[last.clamp(min=0), 1:].reshape(-1)
         return torch.where(last >= 0, pick, carried)
+
+    def sample_stats(self):
+        """per sample [pairs, key_pairs, dupe_pairs, positions, dups, kept]
+        summed over the ranks (every rank calls it and gets the same rows):
+        each row is what a run of the sample's own pairs reports"""
+        import numpy as np
+        rows = np.array([[x.pairs, x.key_pairs, x.dupe_pairs, x.positions, x.dups, x.kept]
+                         for x in self.pipe.sample_stats()], np.int64).reshape(-1, 6)
+        parts = self.comm.all_gather_bytes(rows.tobytes())
+        return sum(np.frombuffer(b, np.int64).reshape(-1, 6) for b in parts).tolist()
 
 
 def open_fastq(sc, r1_paths, r2_paths, sort_names=False, threads=0, read_len=0):
@@ -302,8 +330,57 @@ def count_fastq(sc, index, batch, d_counts, look_ahead=True, pin=True):
     look_ahead the next batch is packed and copied before this one's
     exchange and its search issued with it.  Returns the pairs this rank
     counted."""
+    return _count_plan(sc, index.n, index.L, index.pack, batch, d_counts, look_ahead, pin)
+
+
+def sample_spans(first, lo, hi):
+    """the global pairs [lo, hi) of a plan that is the samples' plans one after
+    the other (sample s = [first[s], first[s + 1])), cut by sample: a list of
+    (s, a, b, at) -- sample s's own pairs [a, b) stand at pair `at` of the
+    share.  Empty samples are passed over."""
+    import bisect
+    out = []
+    q = lo
+    while q < hi:
+        s = bisect.bisect_right(first, q, 0, len(first) - 1) - 1
+        e = min(hi, first[s + 1])
+        out.append((s, q - first[s], e - first[s], q - lo))
+        q = e
+    return out
+
+
+def count_fastq_many(sc, indexes, batch, d_counts, look_ahead=True, pin=True):
+    """count_fastq for a demultiplexed lane: indexes holds one
+    smashgpu.FastqIndex per sample (every rank builds all of them: the
+    rank-local reader for many samples is not built), the global plan is their
+    plans one after the other, and sc was made with samples = the plan's
+    sample starts (sample_first(indexes)).  A rank's share of a step is packed
+    from every sample it overlaps (sample_spans); d_counts is [samples,
+    nbins].  Returns the pairs this rank counted."""
+    first = sample_first(indexes)
+    if sc.samples != first:
+        raise ValueError("count_fastq_many: the counter's sample table is not the indexes' plan")
+    L = indexes[0].L
+
+    def pack(lo, hi, out):
+        for s, a, b, at in sample_spans(first, lo, hi):
+            indexes[s].pack(a, b, out[2 * at:2 * (at + b - a)])
+
+    return _count_plan(sc, first[-1], L, pack, batch, d_counts, look_ahead, pin)
+
+
+def sample_first(indexes):
+    """the sample table of the indexes' plans one after the other"""
+    first = [0]
+    for ix in indexes:
+        first.append(first[-1] + ix.n)
+    return first
+
+
+def _count_plan(sc, n, L, pack, batch, d_counts, look_ahead, pin):
+    """count_fastq's steps over a plan of n pairs of L bases; pack(lo, hi,
+    out) writes planned pairs [lo, hi) into out's first 2 (hi - lo) rows"""
     W, r = sc.world, sc.rank
-    n, L = index.n, index.L
     steps = (n + W * batch - 1) // (W * batch)
     dev = sc.device
     on_dev = dev.type != "cpu"
@@ -318,7 +395,7 @@ def count_fastq(sc, index, batch, d_counts, look_ahead=True, pin=True):
     def load(s, k):   # step s's share into device buffer k (host buffer k reused)
         lo, hi = share(s)
         if hi > lo:
-            index.pack(lo, hi, host[k])
+            pack(lo, hi, host[k])
             devb[k][:2 * (hi - lo)].copy_(host[k][:2 * (hi - lo)], non_blocking=on_dev)
         return hi - lo
 

@@ -579,14 +579,12 @@ def read_manifest(path):
     return out
 
 
-def cmd_count_many(args):
-    """every sample of the manifest in one run (smash_pipeline_samples): the
-    samples' pairs, each name-ordered, are packed one after the other into
-    batches, counted with one sample table, and written per ID"""
-    import torch
-    samples = read_manifest(args.manifest)
+def _many_inputs(args, samples, device):
+    """count-many's inputs: (index, chrom sizes, bins rows, bin starts, max
+    read length or 0, read length, one FastqIndex per sample, the sample
+    table of their plans one after the other)"""
     ref = _ref(args)
-    ix = load_index(ref, args.device, _verify_flags(args))
+    ix = load_index(ref, device, _verify_flags(args))
     cs = S.read_chrom_sizes(args.chrom_sizes or ref + ".bin/chrom_sizes.txt")
     rows, starts = S.read_bins(os.path.join(args.bindir, "bins.txt"))
     M = _max_read_len(args)
@@ -601,6 +599,74 @@ def cmd_count_many(args):
     first = [0]
     for fq in fqs:
         first.append(first[-1] + fq.n)
+    return ix, cs, rows, starts, M, L, fqs, first
+
+
+def _write_many(samples, rows, host_counts, sample_rows):
+    """every ID's files as count writes them; sample_rows: per sample
+    (positions, dups, kept)"""
+    empty = []
+    for (sid, _, _), c, (pos, dups, kept) in zip(samples, host_counts, sample_rows):
+        if kept == 0:   # (count ID stops there with nothing written, varbin.py:96)
+            empty.append(sid)
+            continue
+        write_varbin(rows, c, pos, dups, kept, sid + ".varbin.txt", sid + ".stats.txt")
+    if empty:
+        raise SystemExit("ZeroDivisionError: no read kept (varbin.py:96): " + " ".join(empty))
+
+
+def _count_many_dist(args, samples, world):
+    """count-many over `world` ranks (as _count_files_dist: one process per
+    GPU under torchrun): every rank indexes every sample's FASTQ lists, the
+    global plan is the samples one after the other, and the ranks count their
+    (step, rank) shares of it with the sample table over the global pair
+    indexes (dist.count_fastq_many, smash_pipeline_samples_sharded); counts and
+    per-sample statistics are summed over the ranks; rank 0 writes the files,
+    which are the one-process run's."""
+    import torch
+    import torch.distributed as tdist
+    from dist import ShardedCounter, count_fastq_many
+    rank = int(os.environ.get("RANK", "0"))
+    local = int(os.environ.get("LOCAL_RANK", "0"))
+    dev = torch.device("cuda", local)
+    torch.cuda.set_device(dev)
+    tdist.init_process_group("nccl", device_id=dev)
+    cpu = tdist.new_group(backend="gloo")
+    ix, cs, rows, starts, M, L, fqs, first = _many_inputs(args, samples, local)
+    n = first[-1]
+    B = max(1, min(int(args.batch), n))
+    # (an owner keeps the keys it owns for the whole run: see _count_files_dist)
+    cap = n // world + n // (8 * world) + (1 << 20)
+    pipe = S.Pipeline(ix, cs, starts, L, B, dedup_capacity=cap, var_len=bool(M))
+    counts = torch.zeros((len(fqs), len(starts)), dtype=torch.int64, device=dev)
+    sc = ShardedCounter(pipe, rank, world, dev, count_group=cpu, plan_pairs=n, samples=first)
+    sc.reset()
+    count_fastq_many(sc, fqs, B, counts)
+    st = pipe.stats(raise_on_error=False)
+    bad = torch.tensor([1 if st.error else 0], dtype=torch.int64, device=dev)
+    tdist.all_reduce(counts)
+    tdist.all_reduce(bad)
+    sample_rows = sc.sample_stats()
+    tdist.barrier()
+    tdist.destroy_process_group()
+    if int(bad[0]):
+        raise SystemExit("count-many: a rank recorded a pipeline data error (%s)"
+                         % S.ERRORS.get(st.error, st.error))
+    if rank == 0:
+        _write_many(samples, rows, counts.cpu().numpy(), [r[3:6] for r in sample_rows])
+
+
+def cmd_count_many(args):
+    """every sample of the manifest in one run (smash_pipeline_samples): the
+    samples' pairs, each name-ordered, are packed one after the other into
+    batches, counted with one sample table, and written per ID.  Under
+    torchrun (WORLD_SIZE > 1) the run is dealt to the ranks, as count's."""
+    import torch
+    samples = read_manifest(args.manifest)
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    if world > 1:
+        return _count_many_dist(args, samples, world)
+    ix, cs, rows, starts, M, L, fqs, first = _many_inputs(args, samples, args.device)
     n = first[-1]
     B = max(1, min(int(args.batch), n))
     dev = torch.device("cuda", args.device)
@@ -626,16 +692,8 @@ def cmd_count_many(args):
     st = pipe.stats(raise_on_error=False)
     if st.error:
         raise SystemExit("%s: %s" % (_err_label(st.error), S.ERRORS.get(st.error, st.error)))
-    host_counts = counts.cpu().numpy()
-    empty = []
-    for (sid, _, _), c, ss in zip(samples, host_counts, pipe.sample_stats()):
-        if ss.kept == 0:   # (count ID stops there with nothing written, varbin.py:96)
-            empty.append(sid)
-            continue
-        write_varbin(rows, c, ss.positions, ss.dups, ss.kept, sid + ".varbin.txt",
-                     sid + ".stats.txt")
-    if empty:
-        raise SystemExit("ZeroDivisionError: no read kept (varbin.py:96): " + " ".join(empty))
+    _write_many(samples, rows, counts.cpu().numpy(),
+                [(ss.positions, ss.dups, ss.kept) for ss in pipe.sample_stats()])
 
 
 def cmd_varbin(args):

@@ -50,6 +50,7 @@ EXPORTS = [
     "smash_pipeline_stats", "smash_pipeline_reset", "smash_pipeline_reset_ex", "smash_pipeline_reads_resident", "smash_pipeline_peek",
     "smash_pipeline_var_len", "smash_pipeline_peek_lens", "smash_pipeline_peek_matches",
     "smash_pipeline_samples", "smash_pipeline_sample_stats",
+    "smash_pipeline_samples_sharded", "smash_phase_hdr_words",
     "smash_pipeline_profile", "smash_pipeline_profile_read",
     "smash_pipeline_positions", "smash_bin_positions", "smash_mappability_scan",
     "smash_sam_records", "smash_sam_format", "smash_sam_free",
@@ -219,6 +220,9 @@ def lib():
     L.smash_phase_bin.argtypes = [vp, vp, vp, vp]
     L.smash_pipeline_stats.argtypes = [vp, C.POINTER(Stats)]
     L.smash_pipeline_samples.argtypes = [vp, u64p, C.c_uint32]
+    L.smash_pipeline_samples_sharded.argtypes = [vp, u64p, C.c_uint32]
+    L.smash_phase_hdr_words.argtypes = [vp]
+    L.smash_phase_hdr_words.restype = C.c_uint32
     L.smash_pipeline_sample_stats.argtypes = [vp, C.POINTER(SampleStats), C.c_uint32]
     L.smash_pipeline_reset.argtypes = [vp, vp]
     L.smash_pipeline_reset_ex.argtypes = [vp, C.c_uint32, vp]
@@ -615,8 +619,11 @@ class Pipeline:
     read_stride: the bytes from one mate to the next in the batches (0:
     read_len, dense; read_stride(read_len): native rows, see to_rows)."""
 
-    # u64 words per key in phase_export's headers (SMASH_EXPORT_HDR_WORDS)
+    # u64 words per key in phase_export's headers (SMASH_EXPORT_HDR_WORDS) and
+    # int64 words of phase_positions' tail / phase_bin's prev + 1; both grow
+    # by the sample with a sharded sample table (set_samples_sharded)
     hdr_words = 1
+    tail_words = 2
 
     def __init__(self, index: Index, chrom_sizes: dict, bin_starts, read_len,
                  max_pairs, min_len=20, min_excess=4, hit_window=10000,
@@ -664,6 +671,31 @@ class Pipeline:
         check(lib().smash_pipeline_samples(self.h, _p(f, u64p) if n else None, n),
               "smash_pipeline_samples")
         self.n_samples = n
+        self._phase_mode()
+
+    def set_samples_sharded(self, first):
+        """the sample table of a multi-GPU run (smash_pipeline_samples_sharded):
+        as set_samples, but over the global pair indexes of the whole run --
+        (step, rank, pair), phase_export's global_base -- and the same on every
+        rank.  The phase calls then work per sample: phase_export's headers
+        have hdr_words = 2 words per key, phase_positions writes tail_words =
+        3 words {count, last pos0, its sample}, phase_bin reads {pos0, sample}
+        and adds into a [len(first) - 1, nbins] counts tensor; count_batch*
+        are refused.  sample_stats() is this rank's share."""
+        f = np.ascontiguousarray([] if first is None else first, np.uint64)
+        if f.ndim != 1 or len(f) == 1:
+            raise SmashError("set_samples_sharded: first holds the samples' starts and the "
+                             "run's end")
+        n = max(len(f) - 1, 0)
+        check(lib().smash_pipeline_samples_sharded(self.h, _p(f, u64p) if n else None, n),
+              "smash_pipeline_samples_sharded")
+        self.n_samples = n
+        self._phase_mode()
+
+    def _phase_mode(self):
+        """the phase buffers' widths for the table now set"""
+        self.hdr_words = int(lib().smash_phase_hdr_words(self.h))
+        self.tail_words = 3 if self.hdr_words > 1 else 2
 
     def sample_stats(self):
         """the per-sample counters so far, a list of SampleStats
@@ -776,11 +808,13 @@ class Pipeline:
               "smash_phase_import")
 
     def phase_positions(self, d_tail, stream=None):
+        """d_tail: int64 [tail_words]"""
         check(lib().smash_phase_positions(self.h, _ptr(d_tail), vp(_stream(stream))),
               "smash_phase_positions")
 
     def phase_bin(self, d_prev, d_counts, stream=None):
-        check(lib().smash_phase_bin(self.h, _ptr(d_prev), _ptr(d_counts),
+        """d_prev: int64 [tail_words - 1]; d_counts as count_batch's"""
+        check(lib().smash_phase_bin(self.h, _ptr(d_prev), self._counts(d_counts),
                                     vp(_stream(stream))), "smash_phase_bin")
 
     def reset(self, stream=None, keep_search=False):

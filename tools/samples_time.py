@@ -1,7 +1,7 @@
 """tools/samples_time.py -- many samples in one run (smash_pipeline_samples)
 against one run per sample, on the GPU.
 
-    samples_time.py [--samples S] [--pairs N] [--runs R] [--out FILE.json]
+    samples_time.py [--samples S] [--pairs N] [--runs R] [--sharded] [--out FILE.json]
     samples_time.py --ab [--ab-pairs P] [--ab-runs 64,256,...] [--out FILE.json]
     samples_time.py --parse TRACE.csv FILE.json
 
@@ -12,6 +12,15 @@ resident in HBM, at the batch size bench.fit_batch picks for S * N pairs.
   baseline  per sample: reset, count_batches over its pairs, stats() (the
             counters are the run's, so they are read before the next reset)
   samples   reset, one table, one count_batches over all pairs, sample_stats()
+
+--sharded adds the multi-GPU step at world 1 (dist.ShardedCounter, its
+collectives over a one-rank process group, the next two batches searched
+ahead, as bench.py's SMASH_BENCH_SHARDED=1 step):
+
+  sharded_samples  the table over the global pair indexes
+                   (smash_pipeline_samples_sharded), every batch through the
+                   phase calls, sample_stats(): rows and counters as baseline's
+  sharded_plain    the same pairs through the phase calls without a table
 
 R alternating runs of each after one untimed run of each; per run the wall
 time, the union of the search launches (profile_active) and their difference,
@@ -74,6 +83,7 @@ def main():
     ap.add_argument("--pairs", type=int, default=500_000)
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--ab", action="store_true")
+    ap.add_argument("--sharded", action="store_true")
     ap.add_argument("--ab-pairs", type=int, default=1_000_000)
     ap.add_argument("--ab-runs", default="64,256,1024,4096,16384")
     ap.add_argument("--out", default=None, help="also write the result to this file "
@@ -181,16 +191,69 @@ def main():
         pipe.count_batches(d_reads, P, B, c_new, resident=True)
         return [six(x) for x in pipe.sample_stats()]
 
-    runs = {"baseline": [], "samples": []}
+    forms = [("baseline", baseline), ("samples", samples)]
+    if args.sharded:
+        import socket
+
+        import torch.distributed as tdist
+        from dist import ShardedCounter
+        sock = socket.socket()
+        sock.bind(("127.0.0.1", 0))
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        os.environ.setdefault("MASTER_PORT", str(sock.getsockname()[1]))
+        sock.close()
+        tdist.init_process_group("nccl", rank=0, world_size=1, device_id=dev)
+        cpu = tdist.new_group(backend="gloo")
+        pipe.reset()
+        sc_smp = ShardedCounter(pipe, 0, 1, dev, count_group=cpu, plan_pairs=P, samples=first)
+        sc_plain = ShardedCounter(pipe, 0, 1, dev, count_group=cpu, plan_pairs=P)
+        c_plain = torch.zeros(len(starts), dtype=torch.int64, device=dev)
+        nb = (P + B - 1) // B
+
+        def sharded(sc, counts):
+            counts.zero_()
+            sc.reset()
+            for b in range(nb):
+                b0, b1 = b * B, min(P, (b + 1) * B)
+                n1 = min(P, b1 + B)
+                m1 = min(P, n1 + B)
+                sc.step(d_reads[2 * b0:2 * b1], b1 - b0, b0, counts,
+                        d_reads[2 * b1:2 * n1] if n1 > b1 else None, n1 - b1,
+                        next2_reads=d_reads[2 * n1:2 * m1] if m1 > n1 else None,
+                        next2_pairs=m1 - n1)
+            sc.finish()
+
+        def sharded_samples():
+            sharded(sc_smp, c_new)
+            return [tuple(r) for r in sc_smp.sample_stats()]
+
+        def sharded_plain():
+            sharded(sc_plain, c_plain)
+            return int(pipe.stats().kept)
+
+        forms += [("sharded_samples", sharded_samples), ("sharded_plain", sharded_plain)]
+
+    def prepare(name):
+        """the form's table, set outside the timed region: setting one waits
+        for the device and allocates (baseline clears it, samples sets its own)"""
+        if name.startswith("sharded"):
+            pipe.reset()
+            pipe.set_samples_sharded(first if name == "sharded_samples" else None)
+            pipe.reads_resident(True)
+        else:
+            pipe.reads_resident(False)
+
+    runs = {name: [] for name, _ in forms}
     for i in range(args.runs + 1):   # (the first of each is the warm-up)
-        for name, fn in (("baseline", baseline), ("samples", samples)):
+        for name, fn in forms:
+            prepare(name)
             st, t = timed(fn)
             if i:
                 runs[name].append(t)
-            if name == "samples":
+            if name in ("samples", "sharded_samples"):
                 assert st == base_st, "the samples' counters differ from their own runs'"
                 assert torch.equal(c_new, c_base), "the samples' count rows differ"
-            else:
+            elif name == "baseline":
                 base_st = st
     res.update(samples=nS, pairs_per_sample=n, batch=B, runs=runs)
     for name, rs in runs.items():
@@ -203,6 +266,8 @@ def main():
     if args.out:
         json.dump(res, open(args.out, "w"), indent=1)
     print(json.dumps({k: v for k, v in res.items() if k != "runs"}))
+    if args.sharded:
+        tdist.destroy_process_group()
 
 
 if __name__ == "__main__":
